@@ -19,6 +19,11 @@ multiple candidates, median -> top-k, and weighted FedAvg, and the
 self-scoring at N=1). Total work is fixed as N grows => strong scaling.
 
 Prints ONE JSON line on rank 0 (driver contract).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps rounds, optionally --dump-outputs, print the line. The
+global-model evaluation and the untimed convergence soak run only with
+--full (their fields are null in a plain run's line).
 """
 import argparse
 import gc
@@ -34,6 +39,38 @@ import time
 # parallelism at these kernel sizes.
 
 import torch
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this
+
+
+def dump_outputs(outdir, eng, st) -> None:
+    """Write what the last timed run_round() handed its caller: the
+    committed global model (the engine's flat fp32 parameter vector),
+    the round's protocol results and the committee's selection. A model
+    too large for the budget is written as a fixed, seeded sample of
+    its elements (indices saved alongside)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    stats = np.array([st.epoch, st.global_loss, st.n_updates,
+                      st.n_selected, st.samples_trained], dtype=np.float64)
+    np.save(os.path.join(outdir, "round_stats.npy"), stats)
+    sel = np.array([[eng.origins.index(o), float(w)]
+                    for o, w in eng.last_decision.selected],
+                   dtype=np.float64).reshape(-1, 2)
+    np.save(os.path.join(outdir, "selected.npy"), sel)
+    flat = eng.global_flat.detach().float().cpu().numpy()
+    # budget left for the model: each sampled element costs 4 B of
+    # value + 8 B of index (float64 holds any index below 2^53 exactly)
+    room = DUMP_BUDGET_BYTES - stats.nbytes - sel.nbytes - 4096
+    if flat.nbytes > room:
+        k = room // 12
+        idx = np.sort(np.random.default_rng(0).choice(
+            flat.size, size=k, replace=False))
+        np.save(os.path.join(outdir, "global_model_sample_index.npy"),
+                idx.astype(np.float64))
+        flat = flat[idx]
+    np.save(os.path.join(outdir, "global_model.npy"),
+            np.ascontiguousarray(flat, dtype=np.float32))
 
 
 def main() -> None:
@@ -59,17 +96,30 @@ def main() -> None:
     ap.add_argument("--metrics", default=None,
                     help="write per-round JSONL records to this path")
     ap.add_argument("--eval", action="store_true", help="eval every round")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not "
+                         "need: the global-model test accuracy after the "
+                         "timed rounds and the untimed convergence soak "
+                         "(--soak)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed rounds, write what the last "
+                         "one computed (global model, round results, "
+                         "committee selection) as DIR/<name>.npy")
     ap.add_argument("--soak", type=int, default=None,
-                    help="UNTIMED extra FL rounds run after the timed "
-                         "region (1-GPU runs only) so the record carries "
-                         "a learned accuracy, not a chance-level one; "
-                         "default 1500 for femnist_cnn (~14 s), 0 "
-                         "otherwise")
+                    help="with --full: UNTIMED extra FL rounds run after "
+                         "the timed region (1-GPU runs only) so the "
+                         "record carries a learned accuracy, not a "
+                         "chance-level one; default 1500 for femnist_cnn "
+                         "(~14 s), 0 otherwise")
     ap.add_argument("--phases", action="store_true",
                     help="print per-phase timings of each timed round")
     ap.add_argument("--no-graphs", action="store_true",
                     help="disable the hipGraph-captured train step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.soak and not args.full:
+        ap.error("--soak runs only with --full")
 
     from bflc_amd.config import FLConfig
     from bflc_amd.comm import Transport
@@ -167,7 +217,14 @@ def main() -> None:
     per_round = cfg.needed_update_count * cfg.samples_per_client \
         * cfg.local_epochs
     total_samples = per_round * args.steps
-    acc = eng.evaluate_global()
+
+    # what the last timed round computed, before anything below moves
+    # the model on (replicas are identical, so rank 0 writes)
+    if args.dump_outputs and t.rank == 0:
+        dump_outputs(args.dump_outputs, eng, st)
+
+    # ---- everything below the timed region runs with --full only ----
+    acc = eng.evaluate_global() if args.full else None
 
     # ---- untimed convergence soak (outside the timed region; 1-GPU
     # runs only). A short driver bench otherwise records only a
@@ -175,7 +232,9 @@ def main() -> None:
     # makes the fresh-box record carry a learned accuracy alongside
     # the wall-clock number. Never touches `elapsed`.
     soak = args.soak
-    if soak is None:  # default: GPU femnist runs only (CPU rounds are
+    if not args.full:
+        soak = 0
+    elif soak is None:  # default: GPU femnist runs only (CPU rounds are
         soak = 1500 if (args.model == "femnist_cnn" and use_cuda) else 0
     soak_acc = None
     if soak > 0 and t.world_size == 1:
@@ -204,6 +263,7 @@ def main() -> None:
             "vs_baseline": None,  # reference publishes no perf numbers
             "dtype": "bf16" if use_cuda else "fp32",
             "data": "synthetic",
+            "full": args.full,
             "test_acc": acc,
             "soak_rounds": soak,
             "soak_test_acc": soak_acc,

@@ -1,5 +1,5 @@
 import torch, sys, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bflc_amd.ops import functional as fn
 hip = fn.hip_ops()
 dev = torch.device("cuda:0")

@@ -1,7 +1,7 @@
 """Per-round wall clock + allocator stats (used to isolate a ~35 ms
 CPython gen-2 GC pause; see bench.py's gc pinning)."""
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bflc_amd.config import FLConfig
 from bflc_amd.comm import Transport
 from bflc_amd.data import make_federated

@@ -5,23 +5,21 @@ The reference's only published number is test_acc 0.9214 at epoch 9 on
 the UCI Occupancy CSV (reference imgs/runtime.jpg, README.md:406-410),
 with 5x2 logistic regression, lr 0.001, batch 100, 20 IID shards
 (main.py:32-53,87-88). These tests run the same config on the same CSV
-(available offline inside the reference checkout) through the engine
-and assert the parity bar. Skipped where the CSV is absent (GPU boxes
-get only the repo snapshot).
+(stored as tests/golden/occupancy/datatraining.txt.gz) through the engine
+and assert the parity bar; a missing fixture is a failure, not a skip.
 """
 import os
 import subprocess
 import sys
 
-import pytest
-
 from bflc_amd.data import OCCUPANCY_PATH, occupancy_available
 
-pytestmark = pytest.mark.skipif(
-    not occupancy_available(),
-    reason=f"reference CSV not present at {OCCUPANCY_PATH}")
-
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_fixture_is_inside_the_repository():
+    assert occupancy_available(), OCCUPANCY_PATH
+    assert os.path.abspath(OCCUPANCY_PATH).startswith(REPO + os.sep)
 
 
 def test_loader_matches_reference_split():
