@@ -54,6 +54,13 @@ CONVS = [
     ("r50.c5.3x3", 64, 7, 512, 512, 3, 1, 1),
 ]
 
+# grad-free scoring forwards: one accuracy_t call pushes a scorer's
+# whole 3072-sample shard through the conv stack
+SCORE_CONVS = [
+    ("fe.conv1", 3072, 28, 1, 32, 3, 1, 1),
+    ("fe.conv2", 3072, 14, 32, 64, 3, 1, 1),
+]
+
 # (name, M, K, N) GEMMs (linear layers + eval shapes)
 GEMMS = [
     ("fe.fc1", 1024, 3136, 128),
@@ -99,6 +106,25 @@ def main():
             out[f"bn.{name}.bwd"] = timeit(
                 lambda: h_ops.batchnorm_bwd(y, dy, mean, invstd, g, yb),
                 args.iters)
+
+    # committee-scoring forwards: conv + ReLU + 2x2 pool, fused in the
+    # conv epilogue vs the two kernels it replaces (bitwise equal)
+    for name, n, h, c, k, r, stride, pad in SCORE_CONVS:
+        x = torch.randn(n, h, h, c, device=dev, dtype=torch.bfloat16)
+        w = torch.randn(k, r, r, c, device=dev, dtype=torch.bfloat16) * 0.05
+        b = torch.randn(k, device=dev, dtype=torch.bfloat16)
+        h_ops = O.hip_ops()
+        out[f"score.{name}.route"] = h_ops.conv2d_relu_pool_route(
+            list(x.shape), list(w.shape), stride, pad)
+        out[f"score.{name}.conv_relu"] = timeit(
+            lambda: h_ops.conv2d_fwd(x, w, b, stride, pad, True), args.iters)
+        out[f"score.{name}.conv_relu+pool"] = timeit(
+            lambda: h_ops.maxpool2d_fwd(
+                h_ops.conv2d_fwd(x, w, b, stride, pad, True), 2, 2, False),
+            args.iters)
+        out[f"score.{name}.fused"] = timeit(
+            lambda: h_ops.conv2d_relu_pool_fwd(x, w, b, stride, pad),
+            args.iters)
 
     for name, m, k, n in GEMMS:
         x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)

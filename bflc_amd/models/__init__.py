@@ -59,10 +59,10 @@ class FemnistCNN(FlatModel):
                 ("f2w", (128, c.n_class), "xavier"), ("f2b", (c.n_class,), "zeros")]
 
     def forward(self, x):
-        h = O.conv2d(x, self.p("c1w"), self.p("c1b"), 1, 1, relu=True)
-        h = O.maxpool2d(h, 2)
-        h = O.conv2d(h, self.p("c2w"), self.p("c2b"), 1, 1, relu=True)
-        h = O.maxpool2d(h, 2)
+        # conv + ReLU + 2x2 pool: one fused kernel per stage when grad
+        # mode is off (scoring / eval), the two-op sequence in training
+        h = O.conv2d_relu_pool(x, self.p("c1w"), self.p("c1b"), 1, 1)
+        h = O.conv2d_relu_pool(h, self.p("c2w"), self.p("c2b"), 1, 1)
         h = h.reshape(h.shape[0], -1)
         h = O.linear(h, self.p("f1w"), self.p("f1b"), relu=True)
         return O.linear(h, self.p("f2w"), self.p("f2b"))

@@ -301,6 +301,29 @@ def maxpool2d(x, kernel: int = 2, stride: Optional[int] = None) -> torch.Tensor:
     return _MaxPool2dFn.apply(x, kernel, stride or kernel, want_idx)
 
 
+def conv2d_relu_pool(x, w, b=None, stride: int = 1,
+                     padding: int = 0) -> torch.Tensor:
+    """maxpool2d(conv2d(x, w, b, relu=True), 2).
+
+    With grad mode off on a GPU (committee scoring, sponsor eval) the
+    2x2 pool runs in the conv kernel's epilogue, so the full-resolution
+    activation is never written to HBM and re-read; the result is
+    bitwise the two-op sequence (csrc/hip/conv2d.hip). Training
+    forwards need that activation and the argmax plane for the
+    backward, so under grad mode — and on CPU — this IS the two-op
+    sequence. The grad-mode test sits here, not in a Function.forward
+    (which always runs with grad mode off). BFLC_FUSED_POOL=0 restores
+    the two-op eval path for A/B runs.
+    """
+    import os
+    if x.is_cuda and not torch.is_grad_enabled() and \
+            os.environ.get("BFLC_FUSED_POOL", "1") == "1":
+        bias = b if b is not None else torch.zeros(
+            w.shape[0], device=x.device, dtype=x.dtype)
+        return hip_ops().conv2d_relu_pool_fwd(x, w, bias, stride, padding)
+    return maxpool2d(conv2d(x, w, b, stride, padding, relu=True), 2)
+
+
 class _BatchNormFn(torch.autograd.Function):
     """BatchNorm2d (NHWC, batch-stats mode: train AND eval — no running
     buffers; the FedBN-style simplification so the flat parameter vector

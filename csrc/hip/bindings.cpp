@@ -1,6 +1,7 @@
 // pybind11 bindings for the bflc_amd gfx950 HIP kernels.
 #include <torch/extension.h>
 
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -76,6 +77,11 @@ std::tuple<torch::Tensor, torch::Tensor> maxpool2d_fwd(torch::Tensor x,
 torch::Tensor maxpool2d_bwd(torch::Tensor dy, torch::Tensor idx,
                             std::vector<long> in_shape, long kernel,
                             long stride);
+torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
+                                   torch::Tensor b, long stride, long pad);
+std::string conv2d_relu_pool_route(std::vector<long> x_shape,
+                                   std::vector<long> w_shape, long stride,
+                                   long pad);
 
 // batchnorm.hip
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> batchnorm_fwd(
@@ -155,6 +161,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kernel"), py::arg("stride"),
         py::arg("want_idx") = true);
   m.def("maxpool2d_bwd", &bflc::maxpool2d_bwd);
+  m.def("conv2d_relu_pool_fwd", &bflc::conv2d_relu_pool_fwd,
+        "grad-free conv + bias + ReLU + 2x2/2 maxpool, pooled in the conv "
+        "epilogue where a fused route applies: [N, OH/2, OW/2, Kout]",
+        py::arg("x"), py::arg("w"), py::arg("b"), py::arg("stride"),
+        py::arg("pad"));
+  m.def("conv2d_relu_pool_route", &bflc::conv2d_relu_pool_route,
+        "route conv2d_relu_pool_fwd takes: gemm256_pool | thin_pool | "
+        "unfused",
+        py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
+        py::arg("pad"));
   m.def("batchnorm_fwd", &bflc::batchnorm_fwd,
         py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
         py::arg("relu"), py::arg("residual") = py::none(),

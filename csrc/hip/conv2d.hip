@@ -674,6 +674,77 @@ std::tuple<torch::Tensor, torch::Tensor> maxpool2d_fwd(torch::Tensor x,
   return {y, idx};
 }
 
+// ---- grad-free conv + bias + ReLU + 2x2/stride-2 maxpool ----
+// Committee scoring pushes 4x the training sample volume through the
+// conv stack and never needs the full-resolution activation, which the
+// two-kernel form writes to HBM only for the pool to read back and keep
+// one value in four. The fused routes pool in the conv epilogue; bias
+// add, ReLU and the fp32->bf16 rounding are all monotone, so
+// max(round(relu(v_i))) == round(relu(max(v_i))) and the result is
+// bitwise the two-kernel one. Shapes no fused kernel takes run conv
+// then pool right here, so the entry is always correct.
+namespace {
+
+enum class PoolRoute { kUnfused, kGemm256, kThin };
+
+PoolRoute pool_route(const ConvShape& sh) {
+  if (is_1x1_s1(sh)) return PoolRoute::kUnfused;
+  if (gemm_conv_fwd_pool_eligible(sh)) return PoolRoute::kGemm256;
+  const long kp = (sh.RSC() + 7) / 8 * 8;
+  if (sh.RSC() <= 16 && gemm_thin_conv_pool_eligible(sh, kp))
+    return PoolRoute::kThin;
+  return PoolRoute::kUnfused;
+}
+
+ConvShape make_shape_dims(std::vector<long> xs, std::vector<long> ws,
+                          long stride, long pad) {
+  TORCH_CHECK(xs.size() == 4 && ws.size() == 4, "NHWC x, KRSC w");
+  ConvShape sh;
+  sh.N = (int)xs[0]; sh.H = (int)xs[1]; sh.W = (int)xs[2]; sh.C = (int)xs[3];
+  sh.Kout = (int)ws[0]; sh.R = (int)ws[1]; sh.S = (int)ws[2];
+  sh.stride = (int)stride; sh.pad = (int)pad;
+  sh.OH = (sh.H + 2 * sh.pad - sh.R) / sh.stride + 1;
+  sh.OW = (sh.W + 2 * sh.pad - sh.S) / sh.stride + 1;
+  return sh;
+}
+
+}  // namespace
+
+// Name of the route conv2d_relu_pool_fwd takes for these shapes, so a
+// test cannot pass silently through the fallback.
+std::string conv2d_relu_pool_route(std::vector<long> x_shape,
+                                   std::vector<long> w_shape, long stride,
+                                   long pad) {
+  switch (pool_route(make_shape_dims(x_shape, w_shape, stride, pad))) {
+    case PoolRoute::kGemm256: return "gemm256_pool";
+    case PoolRoute::kThin: return "thin_pool";
+    default: return "unfused";
+  }
+}
+
+torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
+                                   torch::Tensor b, long stride, long pad) {
+  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(w);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "conv: bf16 only");
+  auto sh = make_shape(x, w, stride, pad);
+  const PoolRoute route = pool_route(sh);
+  if (route != PoolRoute::kUnfused) {
+    auto w2 = w.view({(long)sh.Kout, sh.RSC()});
+    auto bc = b.contiguous();
+    auto y = torch::empty({(long)sh.N, (long)sh.OH / 2, (long)sh.OW / 2,
+                           (long)sh.Kout}, x.options());
+    const bool done =
+        route == PoolRoute::kGemm256
+            ? gemm_conv_fwd_pool_raw(x, w2, y, sh, &bc, true)
+            : gemm_thin_conv_pool_raw(
+                  x, pad_w2(w2, (sh.RSC() + 7) / 8 * 8), y, sh, &bc, true);
+    TORCH_CHECK(done, "conv2d_relu_pool: route query and launcher disagree");
+    return y;
+  }
+  auto y = conv2d_fwd(x, w, b, stride, pad, true);
+  return std::get<0>(maxpool2d_fwd(y, 2, 2, false));
+}
+
 torch::Tensor maxpool2d_bwd(torch::Tensor dy, torch::Tensor idx,
                             std::vector<long> in_shape, long kernel,
                             long stride) {

@@ -58,6 +58,21 @@ bool gemm_conv_fwd_raw(const torch::Tensor& x, const torch::Tensor& w2,
                        std::pair<torch::Tensor, torch::Tensor>* bn_stats
                        = nullptr);
 
+// Grad-free conv forward with the 2x2/stride-2 maxpool fused into the
+// epilogue: y is [N, OH/2, OW/2, Kout] and is bitwise what the plain
+// forward followed by the index-free maxpool gives. The *_eligible
+// predicates name the shapes each fused kernel takes (the route query
+// and the launchers share them); *_raw return false otherwise.
+bool gemm_conv_fwd_pool_eligible(const ConvShape& sh);
+bool gemm_conv_fwd_pool_raw(const torch::Tensor& x, const torch::Tensor& w2,
+                            torch::Tensor& y, const ConvShape& sh,
+                            const torch::Tensor* bias, bool relu);
+bool gemm_thin_conv_pool_eligible(const ConvShape& sh, long KT);
+bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
+                             const torch::Tensor& w2p, torch::Tensor& y,
+                             const ConvShape& sh, const torch::Tensor* bias,
+                             bool relu);
+
 // Implicit-GEMM NHWC conv data-gradient: dx[M, C] = dy-gather @ wrot2
 // (wrot2[c][(r,s,kout)] = w[kout][r][s][c], i.e. w.permute(3,1,2,0)
 // viewed [C, R*S*Kout]; r,s indices walk the SAME orientation as the

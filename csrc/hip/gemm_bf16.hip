@@ -538,8 +538,20 @@ constexpr int BKP2 = BK2 + 16;
 // oh = (ih + pad - r) / stride (zero when misaligned/out of range) —
 // no dcol matrix and no col2im pass. B is the pre-permuted
 // wrot[c][(r,s,kout)] = w[kout][r][s][c].
-template <int BM, int BN, int CMODE = 0>
-__launch_bounds__(512, 1)
+// POOL (CMODE 1 only) = fused 2x2/stride-2 maxpool epilogue for
+// grad-free forwards: the tile's row index is WINDOW-MAJOR,
+// m' = ((n*PH + ph)*PW + pw)*4 + dy*2 + dx, so the four conv outputs of
+// one pool window are rows l4*4 + 0..3 of a 16x16 MFMA tile — one
+// lane's f32x4 accumulator. The epilogue rounds each to bf16 exactly as
+// the plain store does, keeps the max and stores ONE value at pooled
+// row m'/4: no cross-lane traffic, no LDS, and the full-resolution
+// activation never reaches HBM. Only the per-granule (n, oh, ow) decode
+// differs from the plain mode; the K-loop gather is shared.
+// (The 128x128 conv-forward tile is LDS-sized for two blocks per CU and
+// sits right at the 128-VGPR line for that; its launch bound asks for
+// 4 waves per SIMD so the extra staging variants cannot push it over.)
+template <int BM, int BN, int CMODE = 0, int POOL = 0>
+__launch_bounds__(512, (CMODE == 1 && BM == 128 && BN == 128) ? 4 : 1)
 __global__ void gemm256_kernel(const bf16* __restrict__ A,
                                const bf16* __restrict__ B,
                                bf16* __restrict__ C, float* __restrict__ Cpart,
@@ -604,9 +616,19 @@ __global__ void gemm256_kernel(const bf16* __restrict__ A,
       const long gm = tile_m + (g >> 3);
       cv_mok[i] = gm < M;
       const long m = cv_mok[i] ? gm : 0;
-      const int ow = (int)(m % csh.OW);
-      const int oh = (int)((m / csh.OW) % csh.OH);
-      const int n = (int)(m / ((long)csh.OW * csh.OH));
+      int ow, oh, n;
+      if (POOL) {  // window-major rows: m = pooled pixel * 4 + dy*2 + dx
+        const long pp = m >> 2;
+        const int q = (int)(m & 3);
+        const int pw_n = csh.OW >> 1, ph_n = csh.OH >> 1;
+        ow = (int)(pp % pw_n) * 2 + (q & 1);
+        oh = (int)((pp / pw_n) % ph_n) * 2 + (q >> 1);
+        n = (int)(pp / ((long)pw_n * ph_n));
+      } else {
+        ow = (int)(m % csh.OW);
+        oh = (int)((m / csh.OW) % csh.OH);
+        n = (int)(m / ((long)csh.OW * csh.OH));
+      }
       cv_rowbase[i] = (long)n * csh.H * csh.W * csh.C;
       cv_ih0[i] = oh * csh.stride - csh.pad;
       cv_iw0[i] = ow * csh.stride - csh.pad;
@@ -636,16 +658,40 @@ __global__ void gemm256_kernel(const bf16* __restrict__ A,
       kd_ss[i] = rs0 - kd_rr[i] * csh.S;
     }
   }
-  auto load_tiles = [&](long k0) {
+  // CMODE 1 stages FULL K-steps (k0 + BK2 <= k_end) without the
+  // gk < k_end guard or the scalar tail loads, and blocks whose whole
+  // tile lies inside the matrix additionally drop the row / column
+  // tests: M is 1e5..1e6 rows and K a few K-steps, so those guards
+  // almost never fire yet cost an exec-mask region each in an
+  // issue-bound loop. The guarded form stays for the partial last
+  // K-step and for edge tiles; every variant stages the same values.
+  // The spatial padding test is real work and stays everywhere.
+  const bool cv_interior =
+      CMODE == 1 && tile_m + BM <= M && tile_n + BN <= N;
+  // block-uniform split of one K-step for the CMODE 1 k-decode carries
+  const int kq_c = CMODE == 1 ? BK2 / csh.C : 0;
+  const int kr_c = CMODE == 1 ? BK2 - kq_c * csh.C : 0;
+  const int kq_r = CMODE == 1 ? kq_c / csh.S : 0;
+  const int kq_s = CMODE == 1 ? kq_c - kq_r * csh.S : 0;
+  // (always_inline: left to its size heuristic the compiler emitted the
+  // 256-wide tiles' staging as a real call, with the register arrays
+  // passed through scratch)
+  auto load_tiles_v = [&](long k0, auto fullk_c, auto inter_c)
+      __attribute__((always_inline)) {
+    constexpr bool FK = CMODE == 1 && decltype(fullk_c)::value;
+    constexpr bool IN = FK && decltype(inter_c)::value;
 #pragma unroll
     for (int i = 0; i < GA; ++i) {
       const int g = tid + i * 512;
       const long gk = k0 + (g & 7) * 8;
       if (CMODE == 1) {
-        bool ok = cv_mok[i] && gk < k_end;
         const int ih = cv_ih0[i] + kd_rr[i];
         const int iw = cv_iw0[i] + kd_ss[i];
-        ok = ok && ih >= 0 && ih < csh.H && iw >= 0 && iw < csh.W;
+        // one predicate, no short-circuit: unsigned compares fold the
+        // >= 0 halves, bitwise & keeps it a single exec-mask region
+        const bool ok = (IN || cv_mok[i]) & (FK || gk < k_end) &
+                        ((unsigned)ih < (unsigned)csh.H) &
+                        ((unsigned)iw < (unsigned)csh.W);
         if (ok) {
           ra[i] = *reinterpret_cast<const bf16x8_t*>(
               &A[cv_rowbase[i] + ((long)ih * csh.W + iw) * csh.C
@@ -654,14 +700,19 @@ __global__ void gemm256_kernel(const bf16* __restrict__ A,
           u16x8_t z = {};
           ra[i] = *reinterpret_cast<const bf16x8_t*>(&z);
         }
-        // advance the decode to this granule's next K-step (carries
-        // only: load calls are monotone in k by exactly BK2)
-        int c8n = kd_in[i] + BK2;
-        int dss = 0;
-        while (c8n >= csh.C) { c8n -= csh.C; ++dss; }
-        kd_in[i] = c8n;
-        kd_ss[i] += dss;
-        while (kd_ss[i] >= csh.S) { kd_ss[i] -= csh.S; ++kd_rr[i]; }
+        // advance the decode to this granule's next K-step. Load calls
+        // are monotone in k by exactly BK2 = kq_c*C + kr_c with
+        // kq_c = kq_r*S + kq_s, all block-uniform, so the carries are
+        // two conditional subtracts (kd_in < C, kd_ss < S hold on
+        // entry) — the per-lane while loops this replaces were two
+        // divergent exec-mask loops per granule per K-step.
+        int c8n = kd_in[i] + kr_c;
+        const int cc = c8n >= csh.C ? 1 : 0;
+        kd_in[i] = c8n - (cc ? csh.C : 0);
+        int ssn = kd_ss[i] + kq_s + cc;
+        const int cs = ssn >= csh.S ? 1 : 0;
+        kd_ss[i] = ssn - (cs ? csh.S : 0);
+        kd_rr[i] += kq_r + cs;
         continue;
       }
       if (CMODE == 2) {
@@ -709,6 +760,15 @@ __global__ void gemm256_kernel(const bf16* __restrict__ A,
       if (GBT < 512 && g >= GBT) break;
       const long gn = tile_n + (g >> 3);
       const long gk = k0 + (g & 7) * 8;
+      if (FK) {
+        if (IN || gn < N) {
+          rb[i] = *reinterpret_cast<const bf16x8_t*>(&B[gn * K + gk]);
+        } else {
+          u16x8_t z = {};
+          rb[i] = *reinterpret_cast<const bf16x8_t*>(&z);
+        }
+        continue;
+      }
       if (gn < N && gk + 8 <= k_end) {
         rb[i] = *reinterpret_cast<const bf16x8_t*>(&B[gn * K + gk]);
       } else {
@@ -721,6 +781,16 @@ __global__ void gemm256_kernel(const bf16* __restrict__ A,
                      : (unsigned short)0;
         rb[i] = *reinterpret_cast<const bf16x8_t*>(&v);
       }
+    }
+  };
+  auto load_tiles = [&](long k0) __attribute__((always_inline)) {
+    using yes = std::integral_constant<bool, true>;
+    using no = std::integral_constant<bool, false>;
+    if (CMODE == 1 && k0 + BK2 <= k_end) {  // block-uniform
+      if (cv_interior) load_tiles_v(k0, yes{}, yes{});
+      else load_tiles_v(k0, yes{}, no{});
+    } else {
+      load_tiles_v(k0, no{}, no{});
     }
   };
   auto write_tiles = [&](int buf) {
@@ -770,6 +840,35 @@ __global__ void gemm256_kernel(const bf16* __restrict__ A,
     }
     __syncthreads();
     cur ^= 1;
+  }
+
+  if (POOL && !Cpart) {
+    // M % 4 == 0 (OH, OW even), so a lane's four rows are all inside
+    // the matrix or all outside. The running max walks the window in
+    // the pool kernel's order (code dy*2 + dx, strict >, from -inf) on
+    // the values the plain epilogue would have stored. Split-K
+    // launches store window-major fp32 partials below and pool in
+    // splitk_reduce_pool_kernel.
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm) {
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn) {
+        const long col = tile_n + wn0 + fn * 16 + l15;
+        const long row0 = tile_m + wm0 + fm * 16 + l4 * 4;
+        if (col >= N || row0 >= M) continue;
+        const float bv = bias ? b2f(bias[col]) : 0.f;
+        float best = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = acc[fm][fn][r] + bv;
+          if (relu) v = fmaxf(v, 0.f);
+          const float f = b2f(f2b(v));
+          if (f > best) best = f;
+        }
+        C[(row0 >> 2) * N + col] = f2b(best);
+      }
+    }
+    return;
   }
 
   if (Cpart) {  // split-K partial store (fp32, plain [M,N] layout)
@@ -1219,6 +1318,73 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ Cpart, int S,
   }
 }
 
+// Which of the two reduce kernels (= which fixed summation order) a
+// plain-store reduce of this size takes.
+bool splitk_reduce_is_vec(long M, long N) {
+  return N % 4 == 0 && M * N >= 131072;
+}
+
+// Split-K reduce of the pooled conv forward (gemm256_kernel POOL):
+// the partials are window-major, so rows 4p..4p+3 are one pool window.
+// One thread per pooled output sums each of its four elements in
+// EXACTLY the order the plain reduce of the same (M, N) would —
+// vec_order: serial ascending s (splitk_reduce_vec_kernel); else the
+// 8-lane tree of splitk_reduce_kernel walked serially — then applies
+// bias/ReLU/bf16 rounding and the pool kernel's running max. Split-K
+// only fires when the launch is a handful of tiles, so the serial
+// walk is never on a hot shape.
+__global__ void splitk_reduce_pool_kernel(const float* __restrict__ Cpart,
+                                          int S, long M, long N,
+                                          bf16* __restrict__ C,
+                                          const bf16* __restrict__ bias,
+                                          int relu, int vec_order) {
+  const long total = M * N;
+  const long totalp = total / 4;
+  long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (; o < totalp; o += stride) {
+    const long p = o / N, col = o - p * N;
+    float best = -INFINITY;
+    for (int r = 0; r < 4; ++r) {
+      const long i = (p * 4 + r) * N + col;
+      float v = 0.f;
+      if (vec_order) {
+        for (int s = 0; s < S; ++s) v += Cpart[(long)s * total + i];
+      } else {
+        for (int sl = 0; sl < 8; ++sl) {
+          float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+          int s = sl;
+          for (; s + 24 < S; s += 32) {
+            a0 += Cpart[(long)s * total + i];
+            a1 += Cpart[(long)(s + 8) * total + i];
+            a2 += Cpart[(long)(s + 16) * total + i];
+            a3 += Cpart[(long)(s + 24) * total + i];
+          }
+          if (s < S) { a0 += Cpart[(long)s * total + i]; s += 8; }
+          if (s < S) { a1 += Cpart[(long)s * total + i]; s += 8; }
+          if (s < S) { a2 += Cpart[(long)s * total + i]; }
+          v += (a0 + a1) + (a2 + a3);
+        }
+      }
+      if (bias) v += b2f(bias[col]);
+      if (relu) v = fmaxf(v, 0.f);
+      const float f = b2f(f2b(v));
+      if (f > best) best = f;
+    }
+    C[o] = f2b(best);
+  }
+}
+
+void launch_splitk_reduce_pool(const float* part, long S, long M, long N,
+                               bf16* c, const bf16* bias, int relu) {
+  const long totalp = M * N / 4;
+  const int blocks = (int)std::min<long>((totalp + 255) / 256, 16384);
+  hipLaunchKernelGGL(splitk_reduce_pool_kernel, dim3(blocks), dim3(256), 0,
+                     cur_stream(), part, (int)S, M, N, c, bias, relu,
+                     splitk_reduce_is_vec(M, N) ? 1 : 0);
+  HIP_CHECK(hipGetLastError());
+}
+
 void launch_splitk_reduce(const float* part, long S, long M, long N,
                           bf16* c, const bf16* bias, int relu,
                           EpStore store, long ohw) {
@@ -1228,7 +1394,7 @@ void launch_splitk_reduce(const float* part, long S, long M, long N,
   // many-slice reduces (dw [16][144] with S~128 -> 3 blocks; routing
   // those here cost ResNet-20 21.0 -> 25.5 ms/round). The 8-lane-tree
   // kernel keeps 8-way S parallelism for them.
-  if (store == EpStore::kPlain && N % 4 == 0 && total >= 131072) {
+  if (store == EpStore::kPlain && splitk_reduce_is_vec(M, N)) {
     const long total4 = total / 4;
     const int blocks = (int)std::min<long>((total4 + 255) / 256, 16384);
     hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3(blocks), dim3(256),
@@ -1602,7 +1768,118 @@ __global__ __launch_bounds__(256) void gemm_thin_conv_kernel(
   }
 }
 
+// Fused conv + bias + ReLU + 2x2/stride-2 maxpool for the thin
+// grad-free forward (3x3, C = 1, stride 1: FEMNIST conv1). One thread
+// per POOLED pixel gathers the 4x4 input patch once (16 taps where the
+// four windows separately read 36), forms the four conv outputs with
+// gemm_thin_conv_kernel's dot — same KT-padded tap order, same packed
+// FMAs, zero taps included — rounds each to bf16 and keeps the pool
+// kernel's running max, so the result is bitwise conv-then-pool while
+// the full-resolution activation never exists. The k loop is outermost
+// so one LDS weight read feeds all four windows.
+template <int KT>
+__global__ __launch_bounds__(256) void gemm_thin_conv_pool_kernel(
+    const bf16* __restrict__ X, const bf16* __restrict__ B,
+    bf16* __restrict__ C, const bf16* __restrict__ bias, ConvShape sh,
+    long MP, int N, int relu) {
+  __shared__ float Bl[32 * 64];
+  __shared__ float bl[64];
+  for (int i = threadIdx.x; i < N * KT; i += blockDim.x)
+    Bl[(i % KT) * 64 + i / KT] = b2f(B[i]);
+  for (int i = threadIdx.x; i < N; i += blockDim.x)
+    bl[i] = bias ? b2f(bias[i]) : 0.f;
+  __syncthreads();
+  const int PW = sh.OW >> 1, PHW = (sh.OH >> 1) * PW;
+  long mp = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (; mp < MP; mp += stride) {
+    const int n = (int)(mp / PHW);
+    const int rem = (int)(mp % PHW);
+    const int ih0 = (rem / PW) * 2 - sh.pad;
+    const int iw0 = (rem % PW) * 2 - sh.pad;
+    f32x2v_t pd[4][4];  // input patch, pre-duplicated for v_pk_fma
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int ih = ih0 + r;
+      const bool okh = ih >= 0 && ih < sh.H;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int iw = iw0 + s;
+        const bool ok = okh && iw >= 0 && iw < sh.W;
+        const float f =
+            ok ? b2f(X[((long)n * sh.H + ih) * sh.W + iw]) : 0.f;
+        pd[r][s] = f32x2v_t{f, f};
+      }
+    }
+    const f32x2v_t zero2 = {0.f, 0.f};
+    for (int n8 = 0; n8 < N; n8 += 8) {
+      f32x8v_t acc[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        acc[q] = *reinterpret_cast<const f32x8v_t*>(&bl[n8]);
+#pragma unroll
+      for (int k = 0; k < KT; ++k) {
+        const f32x8v_t bv =
+            *reinterpret_cast<const f32x8v_t*>(&Bl[k * 64 + n8]);
+        const f32x2v_t* bv2 = reinterpret_cast<const f32x2v_t*>(&bv);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          // tap k = r*3 + s of window q = (dy, dx); k >= 9 is K padding
+          const f32x2v_t a =
+              k < 9 ? pd[(q >> 1) + k / 3][(q & 1) + k % 3] : zero2;
+          f32x2v_t* acc2 = reinterpret_cast<f32x2v_t*>(&acc[q]);
+#pragma unroll
+          for (int p = 0; p < 4; ++p) acc2[p] += bv2[p] * a;
+        }
+      }
+      float best[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) best[j] = -INFINITY;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float v = acc[q][j];
+          if (relu && v < 0.f) v = 0.f;
+          const float f = b2f(f2b(v));
+          if (f > best[j]) best[j] = f;
+        }
+      }
+      bf16x8_t out;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) out[j] = f2b(best[j]);
+      *reinterpret_cast<bf16x8_t*>(&C[mp * N + n8]) = out;
+    }
+  }
+}
+
 }  // namespace
+
+// Fused thin conv + ReLU + 2x2 maxpool: true if handled. Same gate as
+// gemm_thin_conv_raw (on the UNPOOLED M, so the two routes switch at
+// the same shape), restricted to the geometry the kernel unrolls.
+bool gemm_thin_conv_pool_eligible(const ConvShape& sh, long KT) {
+  return sh.R == 3 && sh.S == 3 && sh.C == 1 && sh.stride == 1 &&
+         sh.OH % 2 == 0 && sh.OW % 2 == 0 && KT == 16 &&
+         sh.Kout <= 64 && sh.Kout % 8 == 0 && sh.M() >= 65536;
+}
+
+bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
+                             const torch::Tensor& w2p, torch::Tensor& y,
+                             const ConvShape& sh, const torch::Tensor* bias,
+                             bool relu) {
+  const long KT = w2p.size(1);
+  if (!gemm_thin_conv_pool_eligible(sh, KT)) return false;
+  const long MP = sh.M() / 4;
+  const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
+  const int blocks = (int)std::min<long>((MP + 255) / 256, 16384);
+  hipLaunchKernelGGL((gemm_thin_conv_pool_kernel<16>), dim3(blocks),
+                     dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
+                     (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(), bs,
+                     sh, MP, (int)sh.Kout, relu ? 1 : 0);
+  HIP_CHECK(hipGetLastError());
+  return true;
+}
 
 // Col-free thin conv fwd: true if this shape is handled (the caller
 // falls back to im2col + GEMM otherwise). w2p must already be KT-padded
@@ -1965,7 +2242,7 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
                         torch::Tensor& y, const ConvShape& sh,
                         const torch::Tensor* bias, bool relu,
                         std::pair<torch::Tensor, torch::Tensor>* bn_stats
-                        = nullptr) {
+                        = nullptr, bool pool = false) {
   // CMODE 1 (fwd):   y[M=N*OH*OW][Kout], K = R*S*C, A = x gather
   // CMODE 2 (dgrad): y[M=N*H*W][C],      K = R*S*Kout, A = dy gather
   const long M = CMODE == 1 ? sh.M() : (long)sh.N * sh.H * sh.W;
@@ -1973,6 +2250,9 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
   const long K = CMODE == 1 ? sh.RSC() : (long)sh.R * sh.S * sh.Kout;
   const int inner = CMODE == 1 ? sh.C : sh.Kout;  // granule dimension
   if (inner % 8 != 0 || M < 48) return false;
+  if (pool && (CMODE != 1 || N % 64 != 0 || N < 64 || sh.OH % 2 != 0 ||
+               sh.OW % 2 != 0 || bn_stats))
+    return false;  // fused pool: double-buffered wide-N forward only
   if (N % 64 != 0 || N < 64) {
     // narrow-N convs (ResNet-20's Kout 16/32): implicit gather in the
     // synchronous small-tile kernel — the col read it replaces is the
@@ -2148,7 +2428,21 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
     stp = bn_stats->first.data_ptr<float>();
     stq = bn_stats->second.data_ptr<float>();
   }
+  // pool: same tile / split-K choice as the plain forward of this
+  // shape (M counts the same rows, window-major), so every output
+  // element sees the same accumulation order and the fused result is
+  // bitwise conv-then-pool.
   auto launchc = [&](auto bmv, auto bnv) {
+    if constexpr (CMODE == 1) {
+      if (pool) {
+        hipLaunchKernelGGL(
+            (gemm256_kernel<decltype(bmv)::value, decltype(bnv)::value, 1,
+                            1>),
+            grid, block, 0, cur_stream(), a, b, c, part_ptr, bs, M, N, K,
+            kslice, relu ? 1 : 0, (int)EpStore::kPlain, 0, sh, stp, stq);
+        return;
+      }
+    }
     hipLaunchKernelGGL(
         (gemm256_kernel<decltype(bmv)::value, decltype(bnv)::value, CMODE>),
         grid, block, 0, cur_stream(), a, b, c, part_ptr, bs, M, N, K,
@@ -2169,7 +2463,9 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
     case  64064: launchc(c64i{}, c64i{}); break;
   }
   HIP_CHECK(hipGetLastError());
-  if (S > 1)
+  if (S > 1 && pool)
+    launch_splitk_reduce_pool(part_ptr, S, M, N, c, bs, relu ? 1 : 0);
+  else if (S > 1)
     launch_splitk_reduce(part_ptr, S, M, N, c, bs, relu ? 1 : 0,
                          EpStore::kPlain, 0);
   return true;
@@ -2180,6 +2476,18 @@ bool gemm_conv_fwd_raw(const torch::Tensor& x, const torch::Tensor& w2,
                        const torch::Tensor* bias, bool relu,
                        std::pair<torch::Tensor, torch::Tensor>* bn_stats) {
   return conv_implicit_gemm<1>(x, w2, y, sh, bias, relu, bn_stats);
+}
+
+bool gemm_conv_fwd_pool_eligible(const ConvShape& sh) {
+  return sh.C % 8 == 0 && sh.M() >= 48 && sh.Kout % 64 == 0 &&
+         sh.Kout >= 64 && sh.OH % 2 == 0 && sh.OW % 2 == 0;
+}
+
+bool gemm_conv_fwd_pool_raw(const torch::Tensor& x, const torch::Tensor& w2,
+                            torch::Tensor& y, const ConvShape& sh,
+                            const torch::Tensor* bias, bool relu) {
+  if (!gemm_conv_fwd_pool_eligible(sh)) return false;
+  return conv_implicit_gemm<1>(x, w2, y, sh, bias, relu, nullptr, true);
 }
 
 bool gemm_conv_dgrad_raw(const torch::Tensor& dy, const torch::Tensor& wrot2,
