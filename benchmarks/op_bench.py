@@ -6,7 +6,7 @@ shapes) with CUDA events and prints one JSON blob — a finer-grained
 regression harness than rocprof kernel stats (which mix call sites):
 run it before and after a kernel change and diff the per-shape numbers.
 
-    python benchmarks/op_bench.py [--iters 50] [--model all]
+    python benchmarks/op_bench.py [--iters 50] [--only conv,score,train,gemm]
 """
 import argparse
 import json
@@ -61,6 +61,14 @@ SCORE_CONVS = [
     ("fe.conv2", 3072, 14, 32, 64, 3, 1, 1),
 ]
 
+# training steps: the two FEMNIST conv stages at the trainer batch
+# (4 trainers x 3 batches of 1024 per protocol round); the first stage
+# takes no input gradient
+TRAIN_CONVS = [
+    ("fe.conv1", 1024, 28, 1, 32, 3, 1, 1, False),
+    ("fe.conv2", 1024, 14, 32, 64, 3, 1, 1, True),
+]
+
 # (name, M, K, N) GEMMs (linear layers + eval shapes)
 GEMMS = [
     ("fe.fc1", 1024, 3136, 128),
@@ -73,13 +81,16 @@ GEMMS = [
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--only", default="conv,score,train,gemm",
+                    help="comma-separated sections to run")
     args = ap.parse_args()
+    only = set(args.only.split(","))
     assert torch.cuda.is_available(), "op_bench needs a GPU"
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     out = {}
 
-    for name, n, h, c, k, r, stride, pad in CONVS:
+    for name, n, h, c, k, r, stride, pad in (CONVS if "conv" in only else []):
         x = torch.randn(n, h, h, c, device=dev, dtype=torch.bfloat16)
         w = torch.randn(k, r, r, c, device=dev, dtype=torch.bfloat16) * 0.05
         b = torch.randn(k, device=dev, dtype=torch.bfloat16)
@@ -109,7 +120,8 @@ def main():
 
     # committee-scoring forwards: conv + ReLU + 2x2 pool, fused in the
     # conv epilogue vs the two kernels it replaces (bitwise equal)
-    for name, n, h, c, k, r, stride, pad in SCORE_CONVS:
+    for name, n, h, c, k, r, stride, pad in (SCORE_CONVS if "score" in only
+                                             else []):
         x = torch.randn(n, h, h, c, device=dev, dtype=torch.bfloat16)
         w = torch.randn(k, r, r, c, device=dev, dtype=torch.bfloat16) * 0.05
         b = torch.randn(k, device=dev, dtype=torch.bfloat16)
@@ -126,7 +138,59 @@ def main():
             lambda: h_ops.conv2d_relu_pool_fwd(x, w, b, stride, pad),
             args.iters)
 
-    for name, m, k, n in GEMMS:
+    # training conv + ReLU + 2x2 pool stages: the two-op forward (conv
+    # writes the full plane, pool reads it back) vs the fused one that
+    # also emits the argmax plane, and the old backward chain (unpool,
+    # relu mask + db, conv backward) vs the pooled backward entry
+    for name, n, h, c, k, r, stride, pad, want_dx in (
+            TRAIN_CONVS if "train" in only else []):
+        x = torch.randn(n, h, h, c, device=dev, dtype=torch.bfloat16)
+        w = torch.randn(k, r, r, c, device=dev, dtype=torch.bfloat16) * 0.05
+        b = torch.randn(k, device=dev, dtype=torch.bfloat16) * 0.1
+        h_ops = O.hip_ops()
+        out[f"train.{name}.fwd_route"] = h_ops.conv2d_relu_pool_route(
+            list(x.shape), list(w.shape), stride, pad)
+        out[f"train.{name}.bwd_route"] = h_ops.conv2d_relu_pool_bwd_route(
+            list(x.shape), list(w.shape), stride, pad, want_dx, False)
+        out[f"train.{name}.bwd_route_direct_allowed"] = \
+            h_ops.conv2d_relu_pool_bwd_route(
+                list(x.shape), list(w.shape), stride, pad, want_dx, True)
+        out[f"train.{name}.fwd_two_op"] = timeit(
+            lambda: h_ops.maxpool2d_fwd(
+                h_ops.conv2d_fwd_col(x, w, b, stride, pad, True, False)[0],
+                2, 2, True), args.iters)
+        out[f"train.{name}.fwd_fused_idx"] = timeit(
+            lambda: h_ops.conv2d_relu_pool_fwd_idx(x, w, b, stride, pad),
+            args.iters)
+        yfull = h_ops.conv2d_fwd(x, w, b, stride, pad, True)
+        yp, idx = h_ops.maxpool2d_fwd(yfull, 2, 2, True)
+        dy = torch.randn_like(yp)
+        full = list(yfull.shape)
+
+        def old_chain():
+            dyf = h_ops.maxpool2d_bwd(dy, idx, full, 2, 2)
+            dym, db = h_ops.relu_bwd_colsum(yfull, dyf)
+            return h_ops.conv2d_bwd(x, w, dym, stride, pad, None, False,
+                                    want_dx)
+
+        out[f"train.{name}.bwd_old_chain"] = timeit(old_chain, args.iters)
+        out[f"train.{name}.bwd_pooled"] = timeit(
+            lambda: h_ops.conv2d_relu_pool_bwd(x, w, yp, idx, dy, stride,
+                                               pad, True, want_dx, False),
+            args.iters)
+        out[f"train.{name}.bwd_pooled_direct_allowed"] = timeit(
+            lambda: h_ops.conv2d_relu_pool_bwd(x, w, yp, idx, dy, stride,
+                                               pad, True, want_dx, True),
+            args.iters)
+        out[f"train.{name}.unpool_relu_colsum"] = timeit(
+            lambda: h_ops.pool_relu_bwd_colsum(yp, idx, dy, full),
+            args.iters)
+        if not want_dx:
+            out[f"train.{name}.thin_direct_wgrad"] = timeit(
+                lambda: h_ops.thin_conv_pool_wgrad(x, yp, idx, dy, stride,
+                                                   pad), args.iters)
+
+    for name, m, k, n in (GEMMS if "gemm" in only else []):
         x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
         w = torch.randn(k, n, device=dev, dtype=torch.bfloat16)
         b = torch.randn(n, device=dev, dtype=torch.bfloat16)

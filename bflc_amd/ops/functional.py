@@ -301,19 +301,60 @@ def maxpool2d(x, kernel: int = 2, stride: Optional[int] = None) -> torch.Tensor:
     return _MaxPool2dFn.apply(x, kernel, stride or kernel, want_idx)
 
 
+class _ConvReluPoolFn(torch.autograd.Function):
+    """Training conv + bias + ReLU + 2x2/2 maxpool on the fused GPU
+    routes (csrc/hip/conv2d.hip). The forward pools in the conv
+    epilogue and also emits the u8 argmax plane; only (x, w, y_pooled,
+    idx) are saved — the full-resolution activation never exists. The
+    backward unpools, ReLU-masks by y_pooled > 0 and sums db in one
+    pass, then runs the unchanged conv backward: every gradient is
+    bitwise the two-op path's. With direct_wgrad (BFLC_THIN_DIRECT_WGRAD
+    =1) a thin first layer goes straight to (dw, db) instead, which is
+    faster but sums them in its own order (last-bit differences)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride: int, padding: int,
+                direct_wgrad: bool):
+        ctx.stride, ctx.padding = stride, padding
+        ctx.direct_wgrad = direct_wgrad
+        ctx.has_bias = b is not None
+        bias = b if b is not None else torch.zeros(
+            w.shape[0], device=x.device, dtype=x.dtype)
+        y, idx = hip_ops().conv2d_relu_pool_fwd_idx(x, w, bias, stride,
+                                                    padding)
+        ctx.save_for_backward(x, w, y, idx)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y, idx = ctx.saved_tensors
+        want_dx = ctx.needs_input_grad[0]
+        dx, dw, db = hip_ops().conv2d_relu_pool_bwd(
+            x, w, y, idx, dy.contiguous(), ctx.stride, ctx.padding,
+            ctx.has_bias, want_dx, ctx.direct_wgrad)
+        return (dx if want_dx else None, dw,
+                db if ctx.has_bias else None, None, None, None)
+
+
 def conv2d_relu_pool(x, w, b=None, stride: int = 1,
                      padding: int = 0) -> torch.Tensor:
     """maxpool2d(conv2d(x, w, b, relu=True), 2).
 
-    With grad mode off on a GPU (committee scoring, sponsor eval) the
-    2x2 pool runs in the conv kernel's epilogue, so the full-resolution
-    activation is never written to HBM and re-read; the result is
-    bitwise the two-op sequence (csrc/hip/conv2d.hip). Training
-    forwards need that activation and the argmax plane for the
-    backward, so under grad mode — and on CPU — this IS the two-op
-    sequence. The grad-mode test sits here, not in a Function.forward
-    (which always runs with grad mode off). BFLC_FUSED_POOL=0 restores
-    the two-op eval path for A/B runs.
+    On a GPU the 2x2 pool runs in the conv kernel's epilogue wherever a
+    fused route takes the shape, so the full-resolution activation is
+    never written to HBM and re-read; the pooled result is bitwise the
+    two-op sequence (csrc/hip/conv2d.hip). With grad mode off
+    (committee scoring, sponsor eval) that is the whole op. With grad
+    mode on, _ConvReluPoolFn additionally keeps the argmax plane and
+    runs the fused backward, whose gradients are bitwise the two-op
+    ones; BFLC_THIN_DIRECT_WGRAD=1 opts the thin first layer into the
+    direct weight-gradient kernel (faster, but dW/db of that layer may
+    move in the last bit). The CPU, shapes no fused route takes, and
+    either gate switched off keep the two-op autograd sequence. The
+    grad-mode test sits here, not in a Function.forward (which always
+    runs with grad mode off). BFLC_FUSED_POOL=0 restores the two-op
+    eval path and BFLC_FUSED_POOL_TRAIN=0 the two-op training path for
+    A/B runs.
     """
     import os
     if x.is_cuda and not torch.is_grad_enabled() and \
@@ -321,6 +362,13 @@ def conv2d_relu_pool(x, w, b=None, stride: int = 1,
         bias = b if b is not None else torch.zeros(
             w.shape[0], device=x.device, dtype=x.dtype)
         return hip_ops().conv2d_relu_pool_fwd(x, w, bias, stride, padding)
+    if x.is_cuda and torch.is_grad_enabled() and \
+            os.environ.get("BFLC_FUSED_POOL_TRAIN", "1") != "0" and \
+            hip_ops().conv2d_relu_pool_route(
+                list(x.shape), list(w.shape), stride, padding) != "unfused":
+        return _ConvReluPoolFn.apply(
+            x, w, b, stride, padding,
+            os.environ.get("BFLC_THIN_DIRECT_WGRAD", "0") == "1")
     return maxpool2d(conv2d(x, w, b, stride, padding, relu=True), 2)
 
 

@@ -82,6 +82,23 @@ torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
 std::string conv2d_relu_pool_route(std::vector<long> x_shape,
                                    std::vector<long> w_shape, long stride,
                                    long pad);
+std::tuple<torch::Tensor, torch::Tensor> conv2d_relu_pool_fwd_idx(
+    torch::Tensor x, torch::Tensor w, torch::Tensor b, long stride,
+    long pad);
+std::tuple<torch::Tensor, torch::Tensor> pool_relu_bwd_colsum(
+    torch::Tensor y_pooled, torch::Tensor idx, torch::Tensor dy_pooled,
+    std::vector<long> out_shape);
+std::tuple<torch::Tensor, torch::Tensor> thin_conv_pool_wgrad(
+    torch::Tensor x, torch::Tensor y_pooled, torch::Tensor idx,
+    torch::Tensor dy_pooled, long stride, long pad);
+std::string conv2d_relu_pool_bwd_route(std::vector<long> x_shape,
+                                       std::vector<long> w_shape,
+                                       long stride, long pad, bool want_dx,
+                                       bool allow_direct);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_relu_pool_bwd(
+    torch::Tensor x, torch::Tensor w, torch::Tensor y_pooled,
+    torch::Tensor idx, torch::Tensor dy_pooled, long stride, long pad,
+    bool want_db, bool want_dx, bool allow_direct);
 
 // batchnorm.hip
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> batchnorm_fwd(
@@ -171,6 +188,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "unfused",
         py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
         py::arg("pad"));
+  m.def("conv2d_relu_pool_fwd_idx", &bflc::conv2d_relu_pool_fwd_idx,
+        "training conv + bias + ReLU + 2x2/2 maxpool: (y_pooled, idx), "
+        "same routes as conv2d_relu_pool_fwd",
+        py::arg("x"), py::arg("w"), py::arg("b"), py::arg("stride"),
+        py::arg("pad"));
+  m.def("pool_relu_bwd_colsum", &bflc::pool_relu_bwd_colsum,
+        "unpool + ReLU mask + bias grad in one pass: (dy_full_masked, db)",
+        py::arg("y_pooled"), py::arg("idx"), py::arg("dy_pooled"),
+        py::arg("out_shape"));
+  m.def("thin_conv_pool_wgrad", &bflc::thin_conv_pool_wgrad,
+        "direct first-layer (dw, db) from the pooled tensors",
+        py::arg("x"), py::arg("y_pooled"), py::arg("idx"),
+        py::arg("dy_pooled"), py::arg("stride"), py::arg("pad"));
+  m.def("conv2d_relu_pool_bwd_route", &bflc::conv2d_relu_pool_bwd_route,
+        "route conv2d_relu_pool_bwd takes: thin_direct | unpool",
+        py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
+        py::arg("pad"), py::arg("want_dx"), py::arg("allow_direct") = true);
+  m.def("conv2d_relu_pool_bwd", &bflc::conv2d_relu_pool_bwd,
+        "(dx, dw, db) of the fused conv + ReLU + pool from its saved "
+        "(x, w, y_pooled, idx)",
+        py::arg("x"), py::arg("w"), py::arg("y_pooled"), py::arg("idx"),
+        py::arg("dy_pooled"), py::arg("stride"), py::arg("pad"),
+        py::arg("want_db") = true, py::arg("want_dx") = true,
+        py::arg("allow_direct") = true);
   m.def("batchnorm_fwd", &bflc::batchnorm_fwd,
         py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
         py::arg("relu"), py::arg("residual") = py::none(),

@@ -372,6 +372,193 @@ __global__ void maxpool_nhwc_bwd(const bf16* __restrict__ dy,
   }
 }
 
+// ---- backward of conv + ReLU + 2x2/stride-2 maxpool (training) ----
+// A 2x2/stride-2 window sends each pooled gradient to exactly one
+// full-resolution position, and at that position the activation IS the
+// pooled value, so the ReLU mask of the unpooled gradient is just
+// y_pooled > 0: mask-then-unpool == unpool-then-mask. Neither kernel
+// below reads the full-resolution activation.
+
+// Unpool + ReLU mask + bias-gradient partials in one pass, replacing
+// maxpool_nhwc_vec_bwd -> relu_bwd_colsum_part_vec_kernel. Gather form:
+// one thread per FULL-resolution pixel x 8-channel granule reads its
+// window's pooled dy and y (16 B each) and argmax codes (8 B) — the four
+// pixels of a window share them through L1/L2 — and writes its 16 B of
+// the masked plane once: y > 0 && idx == own code ? dy : 0.
+// The rows, the chunking and the row-lane tree are exactly
+// relu_bwd_colsum_part_vec_kernel's over the same [M, N] plane, so every
+// thread adds the same values in the same order (the zeros included) and
+// db is BITWISE what that chain gives, as is the plane (0.f + dy is the
+// pool backward's own accumulate, so even the zero signs agree).
+__global__ void pool_relu_bwd_colsum_part_kernel(
+    const bf16* __restrict__ yp, const uint8_t* __restrict__ idx,
+    const bf16* __restrict__ dyp, bf16* __restrict__ dx, long M, long N,
+    int H, int W, int G, long chunk_rows, float* __restrict__ part) {
+  const int gi = threadIdx.x % G, rl = threadIdx.x / G;
+  const int RL = (int)blockDim.x / G;
+  const long c8 = ((long)blockIdx.x * G + gi) * 8;
+  const long r0 = (long)blockIdx.y * chunk_rows;
+  const long r1 = min(M, r0 + chunk_rows);
+  const int PH = H >> 1, PW = W >> 1;
+  const bf16 zero = f2b(0.f);
+  float sj[8] = {};
+  if (c8 < N)
+    for (long m = r0 + rl; m < r1; m += RL) {  // m = (n, ih, iw)
+      const int iw = (int)(m % W), ih = (int)((m / W) % H);
+      const long n = m / ((long)W * H);
+      const int code = (ih & 1) * 2 + (iw & 1);
+      const long pm = ((n * PH + (ih >> 1)) * PW + (iw >> 1)) * N + c8;
+      const bf16x8_t yv = *reinterpret_cast<const bf16x8_t*>(&yp[pm]);
+      const bf16x8_t dv = *reinterpret_cast<const bf16x8_t*>(&dyp[pm]);
+      const u8x8_t iv = *reinterpret_cast<const u8x8_t*>(&idx[pm]);
+      bf16x8_t gv;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float a = 0.f;
+        if ((int)iv[j] == code) a += b2f(dv[j]);
+        gv[j] = f2b(a);
+        if (!(b2f(yv[j]) > 0.f)) gv[j] = zero;
+        sj[j] += b2f(gv[j]);
+      }
+      *reinterpret_cast<bf16x8_t*>(&dx[m * N + c8]) = gv;
+    }
+  __shared__ float rs[256][8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) rs[threadIdx.x][j] = sj[j];
+  __syncthreads();
+  for (int h = RL >> 1; h > 0; h >>= 1) {
+    if (rl < h) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        rs[rl * G + gi][j] += rs[(rl + h) * G + gi][j];
+    }
+    __syncthreads();
+  }
+  if (rl == 0 && c8 < N) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      part[(long)blockIdx.y * N + c8 + j] = rs[gi][j];
+  }
+}
+
+// Direct weight + bias gradient of the thin first layer (3x3, C = 1,
+// stride 1) through the pool: no dx is wanted there and dW is Kout x 9
+// numbers, so nothing full-resolution is materialised at all — the
+// im2col matrix, the K = M GEMM, its split-K reduce and the narrow copy
+// are replaced by one pass over (x, pooled y, idx, pooled dy).
+// One thread per pooled pixel x 8-channel granule (G granules x PL
+// pixel-lanes per block) reads the 4x4 input patch once and keeps
+// 8 x (9 dW + 1 db) fp32 accumulators. For each window position q,
+// g_q = (idx == q && y > 0) ? dy : 0 feeds nine FMAs against statically
+// indexed patch taps (no dynamic register indexing). Pixels ascend per
+// lane, then a fixed halving tree over the pixel-lanes in LDS; partials
+// [chunks][Kout][10] go to thin_conv_pool_wgrad_final_kernel.
+constexpr int kWgradAcc = 10;  // 9 taps + db
+
+__global__ __launch_bounds__(256) void thin_conv_pool_wgrad_part_kernel(
+    const bf16* __restrict__ X, const bf16* __restrict__ yp,
+    const uint8_t* __restrict__ idx, const bf16* __restrict__ dyp,
+    ConvShape sh, long MP, int G, long chunk_rows,
+    float* __restrict__ part) {
+  const int tid = threadIdx.x;
+  const int gi = tid % G, pl = tid / G;
+  const int PL = 256 / G;
+  const int N = sh.Kout;
+  const int PW = sh.OW >> 1, PHW = (sh.OH >> 1) * PW;
+  const long r0 = (long)blockIdx.x * chunk_rows;
+  const long r1 = min(MP, r0 + chunk_rows);
+  float acc[8][kWgradAcc] = {};
+  if (pl < PL)
+    for (long mp = r0 + pl; mp < r1; mp += PL) {
+      const long n = mp / PHW;
+      const int rem = (int)(mp % PHW);
+      const int ih0 = (rem / PW) * 2 - sh.pad;
+      const int iw0 = (rem % PW) * 2 - sh.pad;
+      float p[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ih = ih0 + r;
+        const bool okh = ih >= 0 && ih < sh.H;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int iw = iw0 + s;
+          const bool ok = okh && iw >= 0 && iw < sh.W;
+          p[r][s] = ok ? b2f(X[(n * sh.H + ih) * sh.W + iw]) : 0.f;
+        }
+      }
+      const long o = mp * N + gi * 8;
+      const bf16x8_t yv = *reinterpret_cast<const bf16x8_t*>(&yp[o]);
+      const bf16x8_t gv = *reinterpret_cast<const bf16x8_t*>(&dyp[o]);
+      const u8x8_t iv = *reinterpret_cast<const u8x8_t*>(&idx[o]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float g = b2f(yv[j]) > 0.f ? b2f(gv[j]) : 0.f;
+        const int code = (int)iv[j];
+        acc[j][9] += g;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float gq = code == q ? g : 0.f;
+#pragma unroll
+          for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+              acc[j][r * 3 + s] =
+                  fmaf(gq, p[(q >> 1) + r][(q & 1) + s], acc[j][r * 3 + s]);
+        }
+      }
+    }
+  // [accumulator][thread] so a tree step reads consecutive addresses
+  __shared__ float rs[kWgradAcc][256];
+  int plp2 = 1;
+  while (plp2 < PL) plp2 *= 2;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+#pragma unroll
+    for (int a = 0; a < kWgradAcc; ++a) rs[a][tid] = acc[j][a];
+    __syncthreads();
+    for (int h = plp2 >> 1; h > 0; h >>= 1) {
+      if (pl < h && pl + h < PL) {
+#pragma unroll
+        for (int a = 0; a < kWgradAcc; ++a) rs[a][tid] += rs[a][tid + h * G];
+      }
+      __syncthreads();
+    }
+    if (pl == 0) {
+      float* out =
+          &part[((long)blockIdx.x * N + gi * 8 + j) * kWgradAcc];
+#pragma unroll
+      for (int a = 0; a < kWgradAcc; ++a) out[a] = rs[a][tid];
+    }
+    __syncthreads();
+  }
+}
+
+// Reduce the chunk partials: one wave per output (k, tap), each lane
+// sums chunks lane, lane + 64, ... ascending, then a fixed halving tree
+// over the 64 lanes; one rounding to bf16. Tap 9 is the bias gradient.
+__global__ __launch_bounds__(256) void thin_conv_pool_wgrad_final_kernel(
+    const float* __restrict__ part, int chunks, int N,
+    bf16* __restrict__ dw, bf16* __restrict__ db) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int o = blockIdx.x * 4 + wv;  // k * 10 + tap
+  const int total = N * kWgradAcc;
+  float v = 0.f;
+  if (o < total)
+    for (int c = lane; c < chunks; c += 64) v += part[(long)c * total + o];
+  __shared__ float rs[4][64];
+  rs[wv][lane] = v;
+  __syncthreads();
+  for (int h = 32; h > 0; h >>= 1) {
+    if (lane < h) rs[wv][lane] += rs[wv][lane + h];
+    __syncthreads();
+  }
+  if (lane == 0 && o < total) {
+    const int k = o / kWgradAcc, a = o % kWgradAcc;
+    if (a < 9) dw[k * 9 + a] = f2b(rs[wv][0]);
+    else db[k] = f2b(rs[wv][0]);
+  }
+}
+
 inline int ew_grid(long n) {
   return (int)std::min<long>((n + 255) / 256, 16384);
 }
@@ -722,8 +909,13 @@ std::string conv2d_relu_pool_route(std::vector<long> x_shape,
   }
 }
 
-torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
-                                   torch::Tensor b, long stride, long pad) {
+namespace {
+
+// (y_pooled, idx); idx is 0-size unless want_idx. Scoring passes
+// want_idx = false and runs exactly the kernels it ran before.
+std::tuple<torch::Tensor, torch::Tensor> relu_pool_fwd_impl(
+    const torch::Tensor& x, const torch::Tensor& w, const torch::Tensor& b,
+    long stride, long pad, bool want_idx) {
   CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(w);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "conv: bf16 only");
   auto sh = make_shape(x, w, stride, pad);
@@ -733,16 +925,181 @@ torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
     auto bc = b.contiguous();
     auto y = torch::empty({(long)sh.N, (long)sh.OH / 2, (long)sh.OW / 2,
                            (long)sh.Kout}, x.options());
+    auto idx = want_idx
+                   ? torch::empty_like(y, y.options().dtype(at::kByte))
+                   : torch::empty({0}, y.options().dtype(at::kByte));
+    uint8_t* ip = want_idx ? idx.data_ptr<uint8_t>() : nullptr;
     const bool done =
         route == PoolRoute::kGemm256
-            ? gemm_conv_fwd_pool_raw(x, w2, y, sh, &bc, true)
+            ? gemm_conv_fwd_pool_raw(x, w2, y, sh, &bc, true, ip)
             : gemm_thin_conv_pool_raw(
-                  x, pad_w2(w2, (sh.RSC() + 7) / 8 * 8), y, sh, &bc, true);
+                  x, pad_w2(w2, (sh.RSC() + 7) / 8 * 8), y, sh, &bc, true,
+                  ip);
     TORCH_CHECK(done, "conv2d_relu_pool: route query and launcher disagree");
-    return y;
+    return {y, idx};
   }
   auto y = conv2d_fwd(x, w, b, stride, pad, true);
-  return std::get<0>(maxpool2d_fwd(y, 2, 2, false));
+  return maxpool2d_fwd(y, 2, 2, want_idx);
+}
+
+// Geometry thin_conv_pool_wgrad unrolls: the thin pooled forward's,
+// with no minimum-rows gate (the direct kernel has no GEMM to fall
+// back to a better tile for).
+bool thin_wgrad_eligible(const ConvShape& sh) {
+  return sh.R == 3 && sh.S == 3 && sh.C == 1 && sh.stride == 1 &&
+         sh.OH > 0 && sh.OW > 0 && sh.OH % 2 == 0 && sh.OW % 2 == 0 &&
+         sh.Kout <= 64 && sh.Kout % 8 == 0;
+}
+
+void check_pooled(const torch::Tensor& y, const torch::Tensor& idx,
+                  const torch::Tensor& dy) {
+  CHECK_GPU(y); CHECK_GPU(idx); CHECK_GPU(dy);
+  CHECK_CONTIG(y); CHECK_CONTIG(idx); CHECK_CONTIG(dy);
+  TORCH_CHECK(y.scalar_type() == at::kBFloat16 &&
+              dy.scalar_type() == at::kBFloat16 &&
+              idx.scalar_type() == at::kByte,
+              "pooled backward: bf16 y/dy and u8 idx");
+  TORCH_CHECK(y.dim() == 4 && y.sizes() == dy.sizes() &&
+              y.sizes() == idx.sizes(),
+              "pooled backward: y, idx, dy must share one NHWC shape");
+}
+
+}  // namespace
+
+torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
+                                   torch::Tensor b, long stride, long pad) {
+  return std::get<0>(relu_pool_fwd_impl(x, w, b, stride, pad, false));
+}
+
+// Training forward: the same routes, plus the u8 argmax plane the
+// backward needs. Both outputs are bitwise conv2d_fwd(relu) then
+// maxpool2d_fwd(2, 2, want_idx=true).
+std::tuple<torch::Tensor, torch::Tensor> conv2d_relu_pool_fwd_idx(
+    torch::Tensor x, torch::Tensor w, torch::Tensor b, long stride,
+    long pad) {
+  return relu_pool_fwd_impl(x, w, b, stride, pad, true);
+}
+
+// (masked full-resolution dy, db) from the pooled tensors; out_shape is
+// the conv output [N, 2*PH, 2*PW, C]. Both are bitwise maxpool2d_bwd
+// then relu_bwd_colsum: same plane, same chunks, same trees.
+std::tuple<torch::Tensor, torch::Tensor> pool_relu_bwd_colsum(
+    torch::Tensor y_pooled, torch::Tensor idx, torch::Tensor dy_pooled,
+    std::vector<long> out_shape) {
+  check_pooled(y_pooled, idx, dy_pooled);
+  const long n = y_pooled.size(0), PH = y_pooled.size(1),
+             PW = y_pooled.size(2), N = y_pooled.size(3);
+  TORCH_CHECK(N % 8 == 0, "pool_relu_bwd_colsum: C % 8 required");
+  TORCH_CHECK(out_shape.size() == 4 && out_shape[0] == n &&
+              out_shape[1] == 2 * PH && out_shape[2] == 2 * PW &&
+              out_shape[3] == N,
+              "pool_relu_bwd_colsum: out_shape must be [N, 2*PH, 2*PW, C]");
+  const long M = n * PH * PW * 4;  // full-resolution rows
+  auto dx = torch::empty({n, 2 * PH, 2 * PW, N}, dy_pooled.options());
+  auto db = torch::empty({N}, dy_pooled.options());
+  int G = 1;
+  while (G * 2 <= std::min<long>(N / 8, 256)) G *= 2;
+  const int cblocks = (int)ceil_div(N / 8, (long)G);
+  const long rows = colsum_chunk_rows(M, N);  // relu_bwd_colsum's
+  const int chunks = (int)((M + rows - 1) / rows);
+  auto part = torch::empty({chunks, N},
+                           dy_pooled.options().dtype(at::kFloat));
+  if (M > 0) {
+    hipLaunchKernelGGL(pool_relu_bwd_colsum_part_kernel,
+                       dim3(cblocks, chunks), dim3(256), 0, cur_stream(),
+                       (const bf16*)y_pooled.data_ptr(),
+                       idx.data_ptr<uint8_t>(),
+                       (const bf16*)dy_pooled.data_ptr(),
+                       (bf16*)dx.data_ptr(), M, N, (int)(2 * PH),
+                       (int)(2 * PW), G, rows, part.data_ptr<float>());
+    HIP_CHECK(hipGetLastError());
+  }
+  colsum_finalize(part, db);
+  return {dx, db};
+}
+
+// (dw, db) of the thin first layer straight from the pooled tensors.
+std::tuple<torch::Tensor, torch::Tensor> thin_conv_pool_wgrad(
+    torch::Tensor x, torch::Tensor y_pooled, torch::Tensor idx,
+    torch::Tensor dy_pooled, long stride, long pad) {
+  CHECK_GPU(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 4,
+              "thin_conv_pool_wgrad: bf16 NHWC x");
+  check_pooled(y_pooled, idx, dy_pooled);
+  const auto sh = make_shape_dims(
+      x.sizes().vec(), {y_pooled.size(3), 3, 3, x.size(3)}, stride, pad);
+  TORCH_CHECK(thin_wgrad_eligible(sh),
+              "thin_conv_pool_wgrad: 3x3, C == 1, stride 1, even OH/OW, "
+              "Kout % 8 == 0 and Kout <= 64 only");
+  TORCH_CHECK(y_pooled.size(0) == sh.N && y_pooled.size(1) == sh.OH / 2 &&
+              y_pooled.size(2) == sh.OW / 2,
+              "thin_conv_pool_wgrad: pooled shape does not match x");
+  const long MP = sh.M() / 4;
+  const int N = sh.Kout;
+  const int G = N / 8, PL = 256 / G;
+  // about two waves per SIMD over the 256 CUs (512 blocks), at least
+  // one pixel per lane: from the row count, not a device query
+  const long rows = std::max<long>(PL, (MP + 511) / 512);
+  const int chunks = (int)std::max<long>(1, (MP + rows - 1) / rows);
+  auto part = torch::empty({(long)chunks, (long)N, (long)kWgradAcc},
+                           x.options().dtype(at::kFloat));
+  auto dw = torch::empty({(long)N, 3, 3, 1}, x.options());
+  auto db = torch::empty({(long)N}, x.options());
+  hipLaunchKernelGGL(thin_conv_pool_wgrad_part_kernel, dim3(chunks),
+                     dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
+                     (const bf16*)y_pooled.data_ptr(),
+                     idx.data_ptr<uint8_t>(),
+                     (const bf16*)dy_pooled.data_ptr(), sh, MP, G, rows,
+                     part.data_ptr<float>());
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(thin_conv_pool_wgrad_final_kernel,
+                     dim3(ceil_div((long)N * kWgradAcc, 4)), dim3(256), 0,
+                     cur_stream(), part.data_ptr<float>(), chunks, N,
+                     (bf16*)dw.data_ptr(), (bf16*)db.data_ptr());
+  HIP_CHECK(hipGetLastError());
+  return {dw, db};
+}
+
+// Route conv2d_relu_pool_bwd takes, so a test cannot pass through the
+// wrong path: "thin_direct" (allowed, no dx wanted, thin geometry) or
+// "unpool". The unpool route is bitwise the two-op backward; the direct
+// one sums dW/db of the first layer in its own order (last-bit
+// differences), which is why the caller has to allow it.
+std::string conv2d_relu_pool_bwd_route(std::vector<long> x_shape,
+                                       std::vector<long> w_shape,
+                                       long stride, long pad, bool want_dx,
+                                       bool allow_direct) {
+  const auto sh = make_shape_dims(x_shape, w_shape, stride, pad);
+  return allow_direct && !want_dx && thin_wgrad_eligible(sh) ? "thin_direct"
+                                                             : "unpool";
+}
+
+// Backward of conv + bias + ReLU + 2x2/2 maxpool from what the fused
+// forward saved: (dx, dw, db), dx / db 0-size unless wanted.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_relu_pool_bwd(
+    torch::Tensor x, torch::Tensor w, torch::Tensor y_pooled,
+    torch::Tensor idx, torch::Tensor dy_pooled, long stride, long pad,
+    bool want_db, bool want_dx, bool allow_direct) {
+  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(w);
+  const auto sh = make_shape(x, w, stride, pad);
+  TORCH_CHECK(sh.OH % 2 == 0 && sh.OW % 2 == 0 &&
+              y_pooled.dim() == 4 && y_pooled.size(0) == sh.N &&
+              y_pooled.size(1) == sh.OH / 2 &&
+              y_pooled.size(2) == sh.OW / 2 && y_pooled.size(3) == sh.Kout,
+              "conv2d_relu_pool_bwd: pooled shape does not match the conv");
+  auto none = torch::empty({0}, x.options());
+  if (allow_direct && !want_dx && thin_wgrad_eligible(sh)) {
+    auto [dw, db] = thin_conv_pool_wgrad(x, y_pooled, idx, dy_pooled,
+                                         stride, pad);
+    return {none, dw.view(w.sizes()), want_db ? db : none};
+  }
+  auto [dyf, db] = pool_relu_bwd_colsum(
+      y_pooled, idx, dy_pooled,
+      {(long)sh.N, (long)sh.OH, (long)sh.OW, (long)sh.Kout});
+  auto [dx, dw, db_unused] =
+      conv2d_bwd(x, w, dyf, stride, pad, c10::nullopt, false, want_dx);
+  (void)db_unused;
+  return {dx, dw, want_db ? db : none};
 }
 
 torch::Tensor maxpool2d_bwd(torch::Tensor dy, torch::Tensor idx,

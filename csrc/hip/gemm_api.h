@@ -64,14 +64,18 @@ bool gemm_conv_fwd_raw(const torch::Tensor& x, const torch::Tensor& w2,
 // predicates name the shapes each fused kernel takes (the route query
 // and the launchers share them); *_raw return false otherwise.
 bool gemm_conv_fwd_pool_eligible(const ConvShape& sh);
+// idx (optional, [N, OH/2, OW/2, Kout] u8): the training forward also
+// gets the argmax code dy*2 + dx of each window, chosen as
+// maxpool2d_fwd chooses it (strict > from -inf on the rounded values).
 bool gemm_conv_fwd_pool_raw(const torch::Tensor& x, const torch::Tensor& w2,
                             torch::Tensor& y, const ConvShape& sh,
-                            const torch::Tensor* bias, bool relu);
+                            const torch::Tensor* bias, bool relu,
+                            uint8_t* idx = nullptr);
 bool gemm_thin_conv_pool_eligible(const ConvShape& sh, long KT);
 bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
                              const torch::Tensor& w2p, torch::Tensor& y,
                              const ConvShape& sh, const torch::Tensor* bias,
-                             bool relu);
+                             bool relu, uint8_t* idx = nullptr);
 
 // Implicit-GEMM NHWC conv data-gradient: dx[M, C] = dy-gather @ wrot2
 // (wrot2[c][(r,s,kout)] = w[kout][r][s][c], i.e. w.permute(3,1,2,0)
@@ -88,6 +92,10 @@ bool gemm_conv_wgrad_raw(const torch::Tensor& dy2, const torch::Tensor& x,
 
 // colsum: out[n] = sum_m X[m,n]  (bias gradient)
 torch::Tensor colsum_bf16(const torch::Tensor& X);
+// colsum's second pass over fp32 partials [chunks][N] -> bf16 out[N],
+// and the row-chunk length its first pass uses for an [M, N] matrix.
+void colsum_finalize(const torch::Tensor& part, torch::Tensor& out);
+long colsum_chunk_rows(long M, long N);
 // fused relu-backward + bias-grad column sum: (dx, db)
 std::tuple<torch::Tensor, torch::Tensor> relu_bwd_colsum(
     const torch::Tensor& y, const torch::Tensor& dy);

@@ -547,6 +547,10 @@ constexpr int BKP2 = BK2 + 16;
 // row m'/4: no cross-lane traffic, no LDS, and the full-resolution
 // activation never reaches HBM. Only the per-granule (n, oh, ow) decode
 // differs from the plain mode; the K-loop gather is shared.
+// POOL == 2 is the training forward: the same epilogue also stores the
+// argmax code (dy*2 + dx, the lane's accumulator index) to pool_idx. It
+// is a separate instantiation, not a runtime null check, so the scoring
+// kernel (POOL == 1) compiles to exactly what it was.
 // (The 128x128 conv-forward tile is LDS-sized for two blocks per CU and
 // sits right at the 128-VGPR line for that; its launch bound asks for
 // 4 waves per SIMD so the extra staging variants cannot push it over.)
@@ -559,7 +563,8 @@ __global__ void gemm256_kernel(const bf16* __restrict__ A,
                                long K, long kslice, int relu, int store_mode,
                                long ohw, ConvShape csh,
                                float* __restrict__ bn_psum = nullptr,
-                               float* __restrict__ bn_psq = nullptr) {
+                               float* __restrict__ bn_psq = nullptr,
+                               uint8_t* __restrict__ pool_idx = nullptr) {
   // wave grid: 2(M) x 4(N) for BN >= 64; 4(M) x 2(N) for BN == 32
   constexpr int WR = BN >= 64 ? 2 : 4, WC = BN >= 64 ? 4 : 2;
   constexpr int FM = BM / WR / 16, FN = BN / WC / 16;
@@ -858,14 +863,19 @@ __global__ void gemm256_kernel(const bf16* __restrict__ A,
         if (col >= N || row0 >= M) continue;
         const float bv = bias ? b2f(bias[col]) : 0.f;
         float best = -INFINITY;
+        int bi = 0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = acc[fm][fn][r] + bv;
           if (relu) v = fmaxf(v, 0.f);
           const float f = b2f(f2b(v));
-          if (f > best) best = f;
+          if (f > best) {
+            best = f;
+            if (POOL == 2) bi = r;
+          }
         }
         C[(row0 >> 2) * N + col] = f2b(best);
+        if (POOL == 2) pool_idx[(row0 >> 2) * N + col] = (uint8_t)bi;
       }
     }
     return;
@@ -1337,7 +1347,8 @@ __global__ void splitk_reduce_pool_kernel(const float* __restrict__ Cpart,
                                           int S, long M, long N,
                                           bf16* __restrict__ C,
                                           const bf16* __restrict__ bias,
-                                          int relu, int vec_order) {
+                                          int relu, int vec_order,
+                                          uint8_t* __restrict__ idx) {
   const long total = M * N;
   const long totalp = total / 4;
   long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1345,6 +1356,7 @@ __global__ void splitk_reduce_pool_kernel(const float* __restrict__ Cpart,
   for (; o < totalp; o += stride) {
     const long p = o / N, col = o - p * N;
     float best = -INFINITY;
+    int bi = 0;
     for (int r = 0; r < 4; ++r) {
       const long i = (p * 4 + r) * N + col;
       float v = 0.f;
@@ -1369,19 +1381,21 @@ __global__ void splitk_reduce_pool_kernel(const float* __restrict__ Cpart,
       if (bias) v += b2f(bias[col]);
       if (relu) v = fmaxf(v, 0.f);
       const float f = b2f(f2b(v));
-      if (f > best) best = f;
+      if (f > best) { best = f; bi = r; }
     }
     C[o] = f2b(best);
+    if (idx) idx[o] = (uint8_t)bi;  // training forward: argmax code
   }
 }
 
 void launch_splitk_reduce_pool(const float* part, long S, long M, long N,
-                               bf16* c, const bf16* bias, int relu) {
+                               bf16* c, const bf16* bias, int relu,
+                               uint8_t* idx) {
   const long totalp = M * N / 4;
   const int blocks = (int)std::min<long>((totalp + 255) / 256, 16384);
   hipLaunchKernelGGL(splitk_reduce_pool_kernel, dim3(blocks), dim3(256), 0,
                      cur_stream(), part, (int)S, M, N, c, bias, relu,
-                     splitk_reduce_is_vec(M, N) ? 1 : 0);
+                     splitk_reduce_is_vec(M, N) ? 1 : 0, idx);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1634,6 +1648,7 @@ TileCfg pick_tile(long M, long N) {
 // fully unroll in registers.
 typedef __attribute__((ext_vector_type(8))) float f32x8v_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2v_t;
+typedef uint8_t u8x8_t __attribute__((ext_vector_type(8)));
 
 template <int KT>
 __global__ __launch_bounds__(256) void gemm_thin_kernel(
@@ -1777,11 +1792,11 @@ __global__ __launch_bounds__(256) void gemm_thin_conv_kernel(
 // kernel's running max, so the result is bitwise conv-then-pool while
 // the full-resolution activation never exists. The k loop is outermost
 // so one LDS weight read feeds all four windows.
-template <int KT>
+template <int KT, bool IDX>
 __global__ __launch_bounds__(256) void gemm_thin_conv_pool_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ B,
-    bf16* __restrict__ C, const bf16* __restrict__ bias, ConvShape sh,
-    long MP, int N, int relu) {
+    bf16* __restrict__ C, uint8_t* __restrict__ idx,
+    const bf16* __restrict__ bias, ConvShape sh, long MP, int N, int relu) {
   __shared__ float Bl[32 * 64];
   __shared__ float bl[64];
   for (int i = threadIdx.x; i < N * KT; i += blockDim.x)
@@ -1833,8 +1848,9 @@ __global__ __launch_bounds__(256) void gemm_thin_conv_pool_kernel(
         }
       }
       float best[8];
+      int bi[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) best[j] = -INFINITY;
+      for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; bi[j] = 0; }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -1842,13 +1858,22 @@ __global__ __launch_bounds__(256) void gemm_thin_conv_pool_kernel(
           float v = acc[q][j];
           if (relu && v < 0.f) v = 0.f;
           const float f = b2f(f2b(v));
-          if (f > best[j]) best[j] = f;
+          if (f > best[j]) {
+            best[j] = f;
+            if (IDX) bi[j] = q;
+          }
         }
       }
       bf16x8_t out;
 #pragma unroll
       for (int j = 0; j < 8; ++j) out[j] = f2b(best[j]);
       *reinterpret_cast<bf16x8_t*>(&C[mp * N + n8]) = out;
+      if (IDX) {  // training forward: argmax code dy*2 + dx per output
+        u8x8_t oidx;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) oidx[j] = (uint8_t)bi[j];
+        *reinterpret_cast<u8x8_t*>(&idx[mp * N + n8]) = oidx;
+      }
     }
   }
 }
@@ -1867,16 +1892,23 @@ bool gemm_thin_conv_pool_eligible(const ConvShape& sh, long KT) {
 bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
                              const torch::Tensor& w2p, torch::Tensor& y,
                              const ConvShape& sh, const torch::Tensor* bias,
-                             bool relu) {
+                             bool relu, uint8_t* idx) {
   const long KT = w2p.size(1);
   if (!gemm_thin_conv_pool_eligible(sh, KT)) return false;
   const long MP = sh.M() / 4;
   const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
   const int blocks = (int)std::min<long>((MP + 255) / 256, 16384);
-  hipLaunchKernelGGL((gemm_thin_conv_pool_kernel<16>), dim3(blocks),
-                     dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
-                     (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(), bs,
-                     sh, MP, (int)sh.Kout, relu ? 1 : 0);
+  if (idx)
+    hipLaunchKernelGGL((gemm_thin_conv_pool_kernel<16, true>), dim3(blocks),
+                       dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
+                       (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(), idx,
+                       bs, sh, MP, (int)sh.Kout, relu ? 1 : 0);
+  else
+    hipLaunchKernelGGL((gemm_thin_conv_pool_kernel<16, false>), dim3(blocks),
+                       dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
+                       (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(),
+                       (uint8_t*)nullptr, bs, sh, MP, (int)sh.Kout,
+                       relu ? 1 : 0);
   HIP_CHECK(hipGetLastError());
   return true;
 }
@@ -2199,6 +2231,38 @@ torch::Tensor colsum_bf16(const torch::Tensor& X) {
   return out;
 }
 
+// Second colsum pass for partials produced outside this file (the
+// pooled conv backward): out[n] = bf16(sum over chunks of part[k][n]),
+// the same kernels and fixed trees colsum_bf16 ends with.
+void colsum_finalize(const torch::Tensor& part, torch::Tensor& out) {
+  const int chunks = (int)part.size(0);
+  const long N = part.size(1);
+  if (N % 4 == 0) {
+    int G4 = 1;
+    while (G4 * 2 <= std::min<long>(N / 4, 16)) G4 *= 2;
+    hipLaunchKernelGGL(colsum_final_vec_kernel,
+                       dim3(ceil_div(N / 4, (long)G4)), dim3(256), 0,
+                       cur_stream(), part.data_ptr<float>(), chunks, N, G4,
+                       (bf16*)out.data_ptr());
+  } else {
+    hipLaunchKernelGGL(colsum_final_kernel, dim3(ceil_div(N, 32)),
+                       dim3(256), 0, cur_stream(), part.data_ptr<float>(),
+                       chunks, N, (bf16*)out.data_ptr());
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// Row-chunk length colsum_bf16 uses for an [M, N] bf16 matrix (N % 8
+// == 0): a few waves per SIMD across the 256 CUs, from the shape alone.
+long colsum_chunk_rows(long M, long N) {
+  int G = 1;
+  while (G * 2 <= std::min<long>(N / 8, 256)) G *= 2;
+  const int cblocks = (int)ceil_div(N / 8, (long)G);
+  const long target =
+      std::max<long>(1, std::min<long>(768 / std::max(cblocks, 1), 256));
+  return std::max<long>(64, (M + target - 1) / target);
+}
+
 // Fused relu backward + bias-grad column sum over dy viewed [M, N]
 // (N = trailing dim, %8). Returns (dx, db). Bitwise equal to
 // relu_bwd() followed by colsum_bf16() — same masking, same partial
@@ -2242,7 +2306,8 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
                         torch::Tensor& y, const ConvShape& sh,
                         const torch::Tensor* bias, bool relu,
                         std::pair<torch::Tensor, torch::Tensor>* bn_stats
-                        = nullptr, bool pool = false) {
+                        = nullptr, bool pool = false,
+                        uint8_t* pool_idx = nullptr) {
   // CMODE 1 (fwd):   y[M=N*OH*OW][Kout], K = R*S*C, A = x gather
   // CMODE 2 (dgrad): y[M=N*H*W][C],      K = R*S*Kout, A = dy gather
   const long M = CMODE == 1 ? sh.M() : (long)sh.N * sh.H * sh.W;
@@ -2434,6 +2499,16 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
   // bitwise conv-then-pool.
   auto launchc = [&](auto bmv, auto bnv) {
     if constexpr (CMODE == 1) {
+      // split-K launches pool (and pick the argmax) in the reduce
+      if (pool && pool_idx && S == 1) {
+        hipLaunchKernelGGL(
+            (gemm256_kernel<decltype(bmv)::value, decltype(bnv)::value, 1,
+                            2>),
+            grid, block, 0, cur_stream(), a, b, c, part_ptr, bs, M, N, K,
+            kslice, relu ? 1 : 0, (int)EpStore::kPlain, 0, sh, stp, stq,
+            pool_idx);
+        return;
+      }
       if (pool) {
         hipLaunchKernelGGL(
             (gemm256_kernel<decltype(bmv)::value, decltype(bnv)::value, 1,
@@ -2464,7 +2539,8 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
   }
   HIP_CHECK(hipGetLastError());
   if (S > 1 && pool)
-    launch_splitk_reduce_pool(part_ptr, S, M, N, c, bs, relu ? 1 : 0);
+    launch_splitk_reduce_pool(part_ptr, S, M, N, c, bs, relu ? 1 : 0,
+                              pool_idx);
   else if (S > 1)
     launch_splitk_reduce(part_ptr, S, M, N, c, bs, relu ? 1 : 0,
                          EpStore::kPlain, 0);
@@ -2485,9 +2561,10 @@ bool gemm_conv_fwd_pool_eligible(const ConvShape& sh) {
 
 bool gemm_conv_fwd_pool_raw(const torch::Tensor& x, const torch::Tensor& w2,
                             torch::Tensor& y, const ConvShape& sh,
-                            const torch::Tensor* bias, bool relu) {
+                            const torch::Tensor* bias, bool relu,
+                            uint8_t* idx) {
   if (!gemm_conv_fwd_pool_eligible(sh)) return false;
-  return conv_implicit_gemm<1>(x, w2, y, sh, bias, relu, nullptr, true);
+  return conv_implicit_gemm<1>(x, w2, y, sh, bias, relu, nullptr, true, idx);
 }
 
 bool gemm_conv_dgrad_raw(const torch::Tensor& dy, const torch::Tensor& wrot2,
