@@ -95,8 +95,11 @@ def build_hip_ops(force: bool = False) -> Path | None:
     srcs = [hipdir / s for s in HIP_SOURCES if (hipdir / s).exists()]
     if not srcs:
         return None
+    # any header may be included by any source: a newer one makes every
+    # object stale
+    headers = sorted(hipdir.glob("*.h"))
     out = PKG / f"_hip_ops{EXT_SUFFIX}"
-    if not force and _newer(out, srcs):
+    if not force and _newer(out, srcs + headers):
         return out
 
     incs, libdirs, libs = _torch_paths()
@@ -117,7 +120,7 @@ def build_hip_ops(force: bool = False) -> Path | None:
     for s in srcs:
         o = objdir / (s.name + ".o")
         objs.append(o)
-        if _newer(o, [s]) and not force:
+        if _newer(o, [s] + headers) and not force:
             continue
         lang = [] if s.suffix == ".hip" else ["-x", "c++"]
         _run([HIPCC, "-c", *lang, str(s), "-o", str(o)] + common)

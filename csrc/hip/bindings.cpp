@@ -47,6 +47,9 @@ torch::Tensor accuracy_t(torch::Tensor logits, torch::Tensor target);
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
                          bool relu);
 torch::Tensor gemm_raw(torch::Tensor A, torch::Tensor B, bool ta, bool tb);
+using PlanRow = std::tuple<std::string, long, long, long, long>;
+PlanRow gemm_plan_route(long M, long N, long K, bool ta, bool tb);
+std::tuple<long, long, long, long> colsum_geom_query(long M, long N);
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> linear_bwd(
     torch::Tensor x, torch::Tensor w, torch::Tensor dy, bool want_dx);
 
@@ -82,6 +85,8 @@ torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
 std::string conv2d_relu_pool_route(std::vector<long> x_shape,
                                    std::vector<long> w_shape, long stride,
                                    long pad);
+PlanRow conv_plan_route(const std::string& entry, std::vector<long> x_shape,
+                        std::vector<long> w_shape, long stride, long pad);
 std::tuple<torch::Tensor, torch::Tensor> conv2d_relu_pool_fwd_idx(
     torch::Tensor x, torch::Tensor w, torch::Tensor b, long stride,
     long pad);
@@ -147,6 +152,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_fwd", &bflc::linear_fwd, "MFMA bf16 GEMM + bias (+relu)",
         py::arg("x"), py::arg("w"), py::arg("b"), py::arg("relu") = false);
   m.def("gemm_raw", &bflc::gemm_raw, "raw GEMM (bench/ablation)");
+  m.def("gemm_plan_route", &bflc::gemm_plan_route,
+        "plan gemm_raw takes: (thin | gemm8p | gemm256 | small, bm, bn, S, "
+        "kslice)",
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("ta"),
+        py::arg("tb"));
+  m.def("conv_plan_route", &bflc::conv_plan_route,
+        "plan of the implicit-GEMM conv entry fwd | fwd_pool | dgrad | "
+        "wgrad: (none | gemm256 | small, bm, bn, S, kslice)",
+        py::arg("entry"), py::arg("x_shape"), py::arg("w_shape"),
+        py::arg("stride"), py::arg("pad"));
+  m.def("colsum_geom", &bflc::colsum_geom_query,
+        "colsum pass-1 geometry of an [M, N] matrix: (G, cblocks, rows, "
+        "chunks)",
+        py::arg("M"), py::arg("N"));
   m.def("linear_bwd", &bflc::linear_bwd,
         "(dx, dw, db) - dx empty unless want_dx", py::arg("x"),
         py::arg("w"), py::arg("dy"), py::arg("want_dx") = true);

@@ -897,6 +897,20 @@ ConvShape make_shape_dims(std::vector<long> xs, std::vector<long> ws,
 
 }  // namespace
 
+// Plan of an implicit-GEMM conv entry ("fwd", "fwd_pool", "dgrad",
+// "wgrad") for these shapes: (path, bm, bn, S, kslice).
+PlanRow conv_plan_route(const std::string& entry, std::vector<long> x_shape,
+                        std::vector<long> w_shape, long stride, long pad) {
+  const ConvEntry e = entry == "fwd"        ? ConvEntry::kFwd
+                      : entry == "fwd_pool" ? ConvEntry::kFwdPool
+                      : entry == "dgrad"    ? ConvEntry::kDgrad
+                                            : ConvEntry::kWgrad;
+  TORCH_CHECK(e != ConvEntry::kWgrad || entry == "wgrad",
+              "conv_plan_route: entry is fwd | fwd_pool | dgrad | wgrad");
+  return plan_row(
+      gemm_conv_plan(e, make_shape_dims(x_shape, w_shape, stride, pad)));
+}
+
 // Name of the route conv2d_relu_pool_fwd takes for these shapes, so a
 // test cannot pass silently through the fallback.
 std::string conv2d_relu_pool_route(std::vector<long> x_shape,
@@ -997,21 +1011,17 @@ std::tuple<torch::Tensor, torch::Tensor> pool_relu_bwd_colsum(
   const long M = n * PH * PW * 4;  // full-resolution rows
   auto dx = torch::empty({n, 2 * PH, 2 * PW, N}, dy_pooled.options());
   auto db = torch::empty({N}, dy_pooled.options());
-  int G = 1;
-  while (G * 2 <= std::min<long>(N / 8, 256)) G *= 2;
-  const int cblocks = (int)ceil_div(N / 8, (long)G);
-  const long rows = colsum_chunk_rows(M, N);  // relu_bwd_colsum's
-  const int chunks = (int)((M + rows - 1) / rows);
-  auto part = torch::empty({chunks, N},
+  const ColsumGeom g = colsum_geom(M, N);  // relu_bwd_colsum's
+  auto part = torch::empty({g.chunks, N},
                            dy_pooled.options().dtype(at::kFloat));
   if (M > 0) {
     hipLaunchKernelGGL(pool_relu_bwd_colsum_part_kernel,
-                       dim3(cblocks, chunks), dim3(256), 0, cur_stream(),
+                       dim3(g.cblocks, g.chunks), dim3(256), 0, cur_stream(),
                        (const bf16*)y_pooled.data_ptr(),
                        idx.data_ptr<uint8_t>(),
                        (const bf16*)dy_pooled.data_ptr(),
                        (bf16*)dx.data_ptr(), M, N, (int)(2 * PH),
-                       (int)(2 * PW), G, rows, part.data_ptr<float>());
+                       (int)(2 * PW), g.G, g.rows, part.data_ptr<float>());
     HIP_CHECK(hipGetLastError());
   }
   colsum_finalize(part, db);

@@ -4,6 +4,11 @@
 
 #include <torch/extension.h>
 
+#include <string>
+#include <tuple>
+
+#include "gemm_plan.h"
+
 namespace bflc {
 
 // NHWC convolution geometry (shared by conv2d.hip and the implicit-
@@ -42,16 +47,30 @@ void gemm_bf16_raw(const torch::Tensor& A, const torch::Tensor& B,
                    std::pair<torch::Tensor, torch::Tensor>* bn_stats
                    = nullptr);
 
-// Implicit-GEMM NHWC conv forward: y[M, Kout] = im2col(x) @ w2^T with
-// the im2col gather fused into the GEMM's A staging (no col matrix).
-// Requires sh.C % 8 == 0 and Kout % 64 == 0; returns false if the
-// shape cannot take this path (caller materializes col instead).
+// What the route queries report of a plan: (path, bm, bn, S, kslice).
+using PlanRow = std::tuple<std::string, long, long, long, long>;
+inline PlanRow plan_row(const GemmPlan& p) {
+  return {gemm_path_name(p.path), p.bm, p.bn, p.S, p.kslice};
+}
+// The plan gemm_bf16_raw takes for a plain-store call without bn_stats.
+PlanRow gemm_plan_route(long M, long N, long K, bool ta, bool tb);
+
+// The implicit-GEMM conv entries below and the plan each launches
+// (path "none": the entry returns false for this shape). Pure host
+// code: allocates and launches nothing.
+enum class ConvEntry { kFwd, kFwdPool, kDgrad, kWgrad };
+GemmPlan gemm_conv_plan(ConvEntry e, const ConvShape& sh);
+
 // col-free thin conv forward (grad-free path): A gathered from the
 // NHWC window, no im2col matrix. w2p is the KT-padded weight.
 bool gemm_thin_conv_raw(const torch::Tensor& x, const torch::Tensor& w2p,
                         torch::Tensor& y, const ConvShape& sh,
                         const torch::Tensor* bias, bool relu);
 
+// Implicit-GEMM NHWC conv forward: y[M, Kout] = im2col(x) @ w2^T with
+// the im2col gather fused into the GEMM's A staging (no col matrix).
+// Requires sh.C % 8 == 0 and M >= 48; returns false if the shape
+// cannot take this path (caller materializes col instead).
 bool gemm_conv_fwd_raw(const torch::Tensor& x, const torch::Tensor& w2,
                        torch::Tensor& y, const ConvShape& sh,
                        const torch::Tensor* bias, bool relu,
@@ -92,10 +111,9 @@ bool gemm_conv_wgrad_raw(const torch::Tensor& dy2, const torch::Tensor& x,
 
 // colsum: out[n] = sum_m X[m,n]  (bias gradient)
 torch::Tensor colsum_bf16(const torch::Tensor& X);
-// colsum's second pass over fp32 partials [chunks][N] -> bf16 out[N],
-// and the row-chunk length its first pass uses for an [M, N] matrix.
+// colsum's second pass over fp32 partials [chunks][N] -> bf16 out[N];
+// colsum_geom (gemm_plan.h) gives the first pass's chunking.
 void colsum_finalize(const torch::Tensor& part, torch::Tensor& out);
-long colsum_chunk_rows(long M, long N);
 // fused relu-backward + bias-grad column sum: (dx, db)
 std::tuple<torch::Tensor, torch::Tensor> relu_bwd_colsum(
     const torch::Tensor& y, const torch::Tensor& dy);

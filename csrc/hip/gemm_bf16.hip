@@ -1426,8 +1426,6 @@ void launch_splitk_reduce(const float* part, long S, long M, long N,
 // reduces chunks in fixed ascending order. Block = 8 row-lanes x 32
 // columns so each block has 8-way row parallelism (a single serial
 // row-walk per thread was latency-bound at ~300us/call).
-constexpr int kColsumRows = 1024;
-
 // Vectorized pass 1 (N % 8 == 0): RL row-lanes x G 16-B column
 // granules per 256-thread block, fixed pairwise halving tree over the
 // row-lanes (structure-deterministic).
@@ -1587,54 +1585,6 @@ __global__ void colsum_final_kernel(const float* __restrict__ part,
     for (int r = 0; r < 8; ++r) v += red[r][elane];
     out[col] = f2b(v);
   }
-}
-
-// Choose the split-K slice count minimizing estimated GEMM + reduce
-// time: gemm ~ 2MNK/tf scaled by chip fill (block_target blocks fill
-// the 256 CUs at this path's occupancy), reduce ~ (S+1)*M*N*4B at
-// ~6 TB/s. Replaces the fixed-target heuristics that either starved
-// tiny-output wgrads of occupancy or drowned mid-size outputs in
-// partial-buffer traffic.
-long pick_splitk(long M, long N, long K, long tiles, long ksteps,
-                 int block_target, double tf, double* time_out = nullptr) {
-  const long budget = (256L << 20) / std::max<long>(M * N * 4, 1);
-  const long smax = std::min<long>({ksteps, budget, 512});
-  const double work = 2.0 * (double)M * N * K / tf;
-  double best_t = 1e30;
-  long best_s = 1;
-  for (long s = 1; s <= smax; s *= 2) {
-    const double fill =
-        std::min(1.0, (double)(tiles * s) / block_target);
-    // short per-slice K chains never amortize the staging prologue;
-    // the measured reduce pass runs ~2.5 TB/s, not peak HBM
-    const double steps = (double)ksteps / s;
-    const double eff = steps / (steps + 4.0);
-    const double t = work / std::max(fill * eff, 1e-3) +
-                     (s > 1 ? (s + 1.0) * M * N * 4 / 2.5e12 : 0.0);
-    if (t < best_t) { best_t = t; best_s = s; }
-  }
-  if (time_out) *time_out = best_t;
-  return best_s;
-}
-
-struct TileCfg { int bm, bn, wr, wc; };
-
-TileCfg pick_tile(long M, long N) {
-  int bn = N <= 32 ? 32 : (N <= 64 ? 64 : 128);
-  int bm = M <= 48 ? 32 : (M <= 96 ? 64 : 128);
-  // keep >= ~512 tiles when possible by shrinking BM (conv fwd shapes
-  // have huge M, so this rarely triggers; fc shapes are latency-bound
-  // anyway)
-  auto tiles = [&](int m, int n) {
-    return ((M + m - 1) / m) * ((N + n - 1) / n);
-  };
-  while (bm > 32 && tiles(bm, bn) < 512 && M > 4096) bm /= 2;
-  int wr = bm >= 64 ? 2 : (bm == 32 ? 1 : 2);
-  int wc = 2;
-  if (bm == 32) { wr = 1; wc = 4; }
-  if (bn == 32 && bm == 32) { wr = 2; wc = 1; }
-  if (bn == 32 && bm > 32) { wr = 2; wc = 2; }
-  return {bm, bn, wr, wc};
 }
 
 // ---- thin GEMM (K <= 32, N <= 64, both % 8; B in [N][K] layout) ----
@@ -1878,6 +1828,159 @@ __global__ __launch_bounds__(256) void gemm_thin_conv_pool_kernel(
   }
 }
 
+static_assert(BK == kSmallBK && BK2 == kDbufBK,
+              "gemm_plan.h slices K in the kernels' steps");
+
+// ---- runtime plan -> compile-time kernel parameters ----
+// Each mapping is written once; a launcher passes a generic lambda that
+// names its kernel and keeps only what is its own (CMODE, POOL, flags).
+template <int V>
+using ic = std::integral_constant<int, V>;
+
+template <class F>
+void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// thin kernels: (8-padded) K -> KT
+template <class F>
+void dispatch_thin(long K, F&& f) {
+  switch (K) {
+    case 8: f(ic<8>{}); break;
+    case 16: f(ic<16>{}); break;
+    case 24: f(ic<24>{}); break;
+    default: f(ic<32>{}); break;
+  }
+}
+
+// gemm_kernel: f(BM, BN, WR, WC) for the tiles pick_tile can return
+template <class F>
+void dispatch_small(const GemmPlan& p, F&& f) {
+  switch (p.bm * 1000 + p.bn) {
+    case 128128: f(ic<128>{}, ic<128>{}, ic<2>{}, ic<2>{}); break;
+    case 128064: f(ic<128>{}, ic<64>{}, ic<2>{}, ic<2>{}); break;
+    case 128032: f(ic<128>{}, ic<32>{}, ic<2>{}, ic<2>{}); break;
+    case  64128: f(ic<64>{}, ic<128>{}, ic<2>{}, ic<2>{}); break;
+    case  64064: f(ic<64>{}, ic<64>{}, ic<2>{}, ic<2>{}); break;
+    case  64032: f(ic<64>{}, ic<32>{}, ic<2>{}, ic<2>{}); break;
+    case  32128: f(ic<32>{}, ic<128>{}, ic<1>{}, ic<4>{}); break;
+    case  32064: f(ic<32>{}, ic<64>{}, ic<1>{}, ic<4>{}); break;
+    case  32032: f(ic<32>{}, ic<32>{}, ic<2>{}, ic<1>{}); break;
+    default: TORCH_CHECK(false, "no tile config for ", p.bm, "x", p.bn);
+  }
+}
+
+// gemm256_kernel: f(BM, BN) for the tiles plan_dbuf can return
+template <class F>
+void dispatch_dbuf(const GemmPlan& p, F&& f) {
+  switch (p.bm * 1000 + p.bn) {
+    case 256256: f(ic<256>{}, ic<256>{}); break;
+    case 256128: f(ic<256>{}, ic<128>{}); break;
+    case 256064: f(ic<256>{}, ic<64>{}); break;
+    case 128256: f(ic<128>{}, ic<256>{}); break;
+    case 128128: f(ic<128>{}, ic<128>{}); break;
+    case 128064: f(ic<128>{}, ic<64>{}); break;
+    case  64256: f(ic<64>{}, ic<256>{}); break;
+    case  64128: f(ic<64>{}, ic<128>{}); break;
+    case  64064: f(ic<64>{}, ic<64>{}); break;
+    default: TORCH_CHECK(false, "no dbuf tile config for ", p.bm, "x", p.bn);
+  }
+}
+
+// fp32 split-K partials [S, M, N]; ptr stays null for a single slice.
+struct SplitKPart {
+  torch::Tensor buf;
+  float* ptr = nullptr;
+};
+
+SplitKPart alloc_splitk_part(const GemmPlan& p, long M, long N,
+                             const torch::Tensor& like) {
+  SplitKPart part;
+  if (p.S > 1) {
+    part.buf = torch::empty({p.S, M, N}, like.options().dtype(at::kFloat));
+    part.ptr = part.buf.data_ptr<float>();
+  }
+  return part;
+}
+
+// Fused BN partials (psum, psq), one [N] row per tile row; both null
+// (and *out left empty) unless the caller's condition holds.
+struct BnStatsPtrs {
+  float* sum = nullptr;
+  float* sq = nullptr;
+};
+
+BnStatsPtrs alloc_bn_stats(std::pair<torch::Tensor, torch::Tensor>* out,
+                           bool want, const GemmPlan& p, long M, long N,
+                           const torch::Tensor& like) {
+  BnStatsPtrs st;
+  if (out && want) {
+    const long chunks = (M + p.bm - 1) / p.bm;
+    const auto opt = like.options().dtype(at::kFloat);
+    out->first = torch::empty({chunks, N}, opt);
+    out->second = torch::empty({chunks, N}, opt);
+    st.sum = out->first.data_ptr<float>();
+    st.sq = out->second.data_ptr<float>();
+  }
+  return st;
+}
+
+// BFLC_WGRAD_SMALL: -1 never, 1 always, unset/0 = plan_dense's gate.
+int wgrad_small_gate() {
+  static const int v = [] {
+    const char* e = getenv("BFLC_WGRAD_SMALL");
+    return e ? atoi(e) : 0;
+  }();
+  return v;
+}
+
+// Double-buffered narrow-BN conv route (default OFF — measured
+// negative): gemm256_kernel's BN==32 wave grid register-stages
+// K-step t+2 while the MFMAs of t run, the theory being that the
+// sync kernel serializes gather-stage -> barrier -> MFMA at ~10x
+// the traffic bound. A/B on hardware (gpurun_out/r20_kd*.json):
+// ResNet-20 protocol round 67.5 ms dbuf vs 64.0 sync, FEMNIST 9.05
+// vs 9.07 — the sync kernel's 256-thread blocks oversubscribe each
+// CU with multiple blocks, which already hides the stage latency;
+// the 512-thread dbuf blocks halve that block-level parallelism
+// and its staging VALU count is no lower (the real bound —
+// MemUnitStalled ~0, profiles/r02_pmc_femnist.md). Kept behind
+// BFLC_NARROW_DBUF=1 as the documented experiment.
+bool narrow_dbuf_gate() {
+  static const bool v = [] {
+    const char* e = getenv("BFLC_NARROW_DBUF");
+    return e && e[0] == '1';
+  }();
+  return v;
+}
+
+// The GEMM view of the implicit conv entries:
+//   fwd:   y[M=N*OH*OW][Kout], K = R*S*C,    A = x gather
+//   dgrad: y[M=N*H*W][C],      K = R*S*Kout, A = dy gather
+//   wgrad: dW[Kout][R*S*C],    K = N*OH*OW,  B = x gather
+struct GemmDims { long M, N, K; };
+
+GemmDims conv_gemm_dims(ConvEntry e, const ConvShape& sh) {
+  if (e == ConvEntry::kWgrad) return {sh.Kout, sh.RSC(), sh.M()};
+  if (e == ConvEntry::kDgrad)
+    return {(long)sh.N * sh.H * sh.W, sh.C, (long)sh.R * sh.S * sh.Kout};
+  return {sh.M(), sh.Kout, sh.RSC()};
+}
+
+void launch_colsum_final(const float* part, int chunks, long N, bf16* out) {
+  if (N % 4 == 0) {
+    const int G4 = colsum_final_g4(N);
+    hipLaunchKernelGGL(colsum_final_vec_kernel,
+                       dim3(ceil_div(N / 4, (long)G4)), dim3(256), 0,
+                       cur_stream(), part, chunks, N, G4, out);
+  } else {
+    hipLaunchKernelGGL(colsum_final_kernel, dim3(ceil_div(N, 32)),
+                       dim3(256), 0, cur_stream(), part, chunks, N, out);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
 
 // Fused thin conv + ReLU + 2x2 maxpool: true if handled. Same gate as
@@ -1898,17 +2001,13 @@ bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
   const long MP = sh.M() / 4;
   const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
   const int blocks = (int)std::min<long>((MP + 255) / 256, 16384);
-  if (idx)
-    hipLaunchKernelGGL((gemm_thin_conv_pool_kernel<16, true>), dim3(blocks),
-                       dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
-                       (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(), idx,
-                       bs, sh, MP, (int)sh.Kout, relu ? 1 : 0);
-  else
-    hipLaunchKernelGGL((gemm_thin_conv_pool_kernel<16, false>), dim3(blocks),
-                       dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
-                       (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(),
-                       (uint8_t*)nullptr, bs, sh, MP, (int)sh.Kout,
-                       relu ? 1 : 0);
+  dispatch_bool(idx != nullptr, [&](auto want_idx) {
+    hipLaunchKernelGGL(
+        (gemm_thin_conv_pool_kernel<16, decltype(want_idx)::value>),
+        dim3(blocks), dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
+        (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(), idx, bs, sh, MP,
+        (int)sh.Kout, relu ? 1 : 0);
+  });
   HIP_CHECK(hipGetLastError());
   return true;
 }
@@ -1926,19 +2025,13 @@ bool gemm_thin_conv_raw(const torch::Tensor& x, const torch::Tensor& w2p,
     return false;
   const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
   const int blocks = (int)std::min<long>((M + 255) / 256, 16384);
-  auto launch = [&](auto kv) {
-    hipLaunchKernelGGL((gemm_thin_conv_kernel<decltype(kv)::value>),
+  dispatch_thin(KT, [&](auto kt) {
+    hipLaunchKernelGGL((gemm_thin_conv_kernel<decltype(kt)::value>),
                        dim3(blocks), dim3(256), 0, cur_stream(),
                        (const bf16*)x.data_ptr(),
                        (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(),
                        bs, sh, M, (int)N, relu ? 1 : 0);
-  };
-  switch (KT) {
-    case 8: launch(std::integral_constant<int, 8>{}); break;
-    case 16: launch(std::integral_constant<int, 16>{}); break;
-    case 24: launch(std::integral_constant<int, 24>{}); break;
-    default: launch(std::integral_constant<int, 32>{}); break;
-  }
+  });
   HIP_CHECK(hipGetLastError());
   return true;
 }
@@ -1965,269 +2058,99 @@ void gemm_bf16_raw(const torch::Tensor& A, const torch::Tensor& B,
   const bf16* b = (const bf16*)B.data_ptr();
   bf16* c = (bf16*)C.data_ptr();
   const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
+  const int relu_i = relu ? 1 : 0, sm = (int)store;
 
-  // thin memory-shaped GEMMs (conv stems after K padding: FEMNIST
-  // conv1 K=16 N=32, CIFAR stems K=32 N=16) bypass the MFMA tilers
-  if (!ta && tb && K <= 32 && K % 8 == 0 && N <= 64 && N % 8 == 0 &&
-      M >= 65536 && store == EpStore::kPlain && !bn_stats) {
-    const int blocks = (int)std::min<long>((M + 255) / 256, 16384);
-    auto launch_thin = [&](auto kv) {
-      hipLaunchKernelGGL((gemm_thin_kernel<decltype(kv)::value>),
-                         dim3(blocks), dim3(256), 0, cur_stream(), a, b, c,
-                         bs, M, (int)N, relu ? 1 : 0);
-    };
-    switch (K) {
-      case 8: launch_thin(std::integral_constant<int, 8>{}); break;
-      case 16: launch_thin(std::integral_constant<int, 16>{}); break;
-      case 24: launch_thin(std::integral_constant<int, 24>{}); break;
-      default: launch_thin(std::integral_constant<int, 32>{}); break;
-    }
+  const GemmPlan p =
+      plan_dense(M, N, K, ta, tb, store == EpStore::kPlain,
+                 bn_stats != nullptr, wgrad_small_gate());
+  if (p.path == GemmPath::kThin) {
+    dispatch_thin(K, [&](auto kt) {
+      hipLaunchKernelGGL((gemm_thin_kernel<decltype(kt)::value>),
+                         dim3((unsigned)p.tiles), dim3(256), 0, cur_stream(),
+                         a, b, c, bs, M, (int)N, relu_i);
+    });
     HIP_CHECK(hipGetLastError());
     return;
   }
 
-  // ---- double-buffered BMxBN path (M bounds-guarded; needs N % 64
-  // and K % 64). Tile + split-K chosen together by the cost model;
-  // per-tile efficiency from the measured ladder (64-tile structures
-  // run far below the 256 ones).
-  // (a BN=32 config measured slower than the synchronous 128x32 path
-  // on the shallow-K shapes it would serve; BN=64 stays the floor, and
-  // N edges are zero-staged + epilogue-guarded like M edges)
-  // N%64 floor: widening to N%8 routed mid shapes onto narrow-BN
-  // configs that measured slower than the synchronous path (the edge
-  // guards stay for M and the K tail).
-  // Route wgrad-layout GEMMs (ta, !tb — both operands K-major) straight
-  // to the small kernel's swizzled scatter staging when the two operand
-  // transposes the dbuf path would need outweigh the GEMM itself:
-  // t_transpose ~ 4K(M+N)/5e12 vs t_gemm ~ 2MNK/600e12, i.e. when
-  // 480(M+N) > MN (all wgrad outputs qualify; big square GEMMs do not).
-  // BFLC_WGRAD_SMALL: -1 never, 1 always, unset/0 = this gate.
-  // (A/B on ResNet-50: 81.2 default-off vs 80.7 ms/round routed small.)
-  static const int wgrad_small = [] {
-    const char* e = getenv("BFLC_WGRAD_SMALL");
-    return e ? atoi(e) : 0;
-  }();
-  const bool route_small =
-      ta && !tb &&
-      (wgrad_small == 1 ||
-       (wgrad_small == 0 && 480.0 * (double)(M + N) > (double)M * N));
-  const bool dbuf_ok = !route_small;
-  if (dbuf_ok &&
-      N % 64 == 0 && K % 8 == 0 && M >= 48 && N >= 64 && K >= 32) {
-    const long ksteps64 = (K + BK2 - 1) / BK2;
-    const int bn2 = (N % 256 == 0) ? 256
-                    : (N % 128 == 0 ? 128 : 64);
-    const long ntn2 = (N + bn2 - 1) / bn2;
-    int bm2 = 256;
-    long S = 1;
-    {
-      double best_t = 1e30;
-      // rough per-tile efficiency from the measured ladder; narrow
-      // tiles are staging-heavier
-      const double bn_pen = bn2 >= 128 ? 1.0 : (bn2 == 64 ? 0.75 : 0.5);
-      for (int bm : (bn2 == 64 ? std::initializer_list<int>{128, 64}
-                               : std::initializer_list<int>{256, 128, 64})) {
-        const double tf = (bm == 256 ? 800.0e12
-                                     : (bm == 128 ? 600.0e12 : 320.0e12)) *
-                          bn_pen;
-        const long tiles_c = ((M + bm - 1) / bm) * ntn2;
-        double t;
-        const long s = pick_splitk(M, N, K, tiles_c, ksteps64, 256, tf, &t);
-        if (t < best_t) { best_t = t; bm2 = bm; S = s; }
-      }
-    }
-    const long tiles = ((M + bm2 - 1) / bm2) * ntn2;
-    const long kslice = ((ksteps64 + S - 1) / S) * BK2;
-    S = (K + kslice - 1) / kslice;
-
-    torch::Tensor part;
-    float* part_ptr = nullptr;
-    if (S > 1) {
-      part = torch::empty({S, M, N}, A.options().dtype(at::kFloat));
-      part_ptr = part.data_ptr<float>();
-    }
+  const SplitKPart part = alloc_splitk_part(p, M, N, A);
+  const dim3 grid((unsigned)p.tiles, (unsigned)p.S);
+  if (p.path == GemmPath::kSmall) {
+    const int vecA = ta ? (M % 8 == 0) : (K % 8 == 0);
+    const int vecB = tb ? (K % 8 == 0) : (N % 8 == 0);
+    dispatch_small(p, [&](auto bm, auto bn, auto wr, auto wc) {
+      constexpr int BMv = decltype(bm)::value, BNv = decltype(bn)::value;
+      constexpr int WRv = decltype(wr)::value, WCv = decltype(wc)::value;
+      dispatch_bool(ta, [&](auto tav) {
+        dispatch_bool(tb, [&](auto tbv) {
+          hipLaunchKernelGGL(
+              (gemm_kernel<BMv, BNv, WRv, WCv, decltype(tav)::value,
+                           decltype(tbv)::value>),
+              grid, dim3(WRv * WCv * 64), 0, cur_stream(), a, b, c, part.ptr,
+              bs, M, N, K, p.kslice, relu_i, sm, ohw, vecA, vecB,
+              ConvShape{});
+        });
+      });
+    });
+  } else {
     // Pre-transpose any operand whose layout would need scalar scatter
     // LDS staging: the all-vector (A [M][K], B [N][K]) kernel measured
     // 819 TF vs 137-242 TF for the scatter layouts at 4096^3, and the
     // tiled transpose costs ~2 round trips of the operand (~5% here).
     torch::Tensor At, Bt;
-    const bf16* a2 = a;
-    const bf16* b2 = b;
-    if (ta) { At = transpose_bf16(A); a2 = (const bf16*)At.data_ptr(); }
-    if (!tb) { Bt = transpose_bf16(B); b2 = (const bf16*)Bt.data_ptr(); }
-
-    dim3 grid((unsigned)tiles, (unsigned)S);
-    dim3 block(512);
-    const int sm = (int)store;
-    float* stp = nullptr;
-    float* stq = nullptr;
-    if (bn_stats && S == 1 && store == EpStore::kPlain) {
-      const long chunks = (M + bm2 - 1) / bm2;
-      bn_stats->first = torch::empty({chunks, N},
-                                     A.options().dtype(at::kFloat));
-      bn_stats->second = torch::empty({chunks, N},
-                                      A.options().dtype(at::kFloat));
-      stp = bn_stats->first.data_ptr<float>();
-      stq = bn_stats->second.data_ptr<float>();
-    }
-    // fully aligned large shapes take the 8-phase glds schedule
-    // (also at shallow K: an A/B routing K-slices < 8 tiles to the
-    // double-buffered kernel measured +9% on a ResNet-50 round)
-    if (bm2 == 256 && bn2 == 256 && M % 256 == 0 && N % 256 == 0 &&
-        K % 64 == 0 && store == EpStore::kPlain) {
-      hipLaunchKernelGGL(gemm8p_kernel, grid, block, 0, cur_stream(), a2,
-                         b2, c, part_ptr, bs, M, N, K, kslice,
-                         relu ? 1 : 0, stp, stq);
-      HIP_CHECK(hipGetLastError());
-      if (S > 1)
-        launch_splitk_reduce(part_ptr, S, M, N, c, bs, relu ? 1 : 0,
-                             store, ohw);
-      return;
-    }
-    auto launch2 = [&](auto bmv, auto bnv) {
-      hipLaunchKernelGGL(
-          (gemm256_kernel<decltype(bmv)::value, decltype(bnv)::value>),
-          grid, block, 0, cur_stream(), a2, b2, c, part_ptr, bs, M, N, K,
-          kslice, relu, sm, ohw, ConvShape{}, stp, stq);
-    };
-    using c64i = std::integral_constant<int, 64>;
-    using c128i = std::integral_constant<int, 128>;
-    using c256i = std::integral_constant<int, 256>;
-    using c32i = std::integral_constant<int, 32>;
-    switch (bm2 * 1000 + bn2) {
-      case 256256: launch2(c256i{}, c256i{}); break;
-      case 256128: launch2(c256i{}, c128i{}); break;
-      case 256064: launch2(c256i{}, c64i{}); break;
-      case 256032: launch2(c256i{}, c32i{}); break;
-      case 128256: launch2(c128i{}, c256i{}); break;
-      case 128128: launch2(c128i{}, c128i{}); break;
-      case 128064: launch2(c128i{}, c64i{}); break;
-      case 128032: launch2(c128i{}, c32i{}); break;
-      case  64256: launch2(c64i{}, c256i{}); break;
-      case  64128: launch2(c64i{}, c128i{}); break;
-      case  64064: launch2(c64i{}, c64i{}); break;
-      case  64032: launch2(c64i{}, c32i{}); break;
-    }
-    HIP_CHECK(hipGetLastError());
-    if (S > 1)
-      launch_splitk_reduce(part_ptr, S, M, N, c, bs, relu ? 1 : 0, store,
-                           ohw);
-    return;
-  }
-
-  const TileCfg t = pick_tile(M, N);
-  const long tiles = ((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
-
-  // split-K when the tile grid cannot fill the chip and K is deep
-  const long ksteps = (K + BK - 1) / BK;
-  long S = pick_splitk(M, N, K, tiles, ksteps, 512, 150.0e12);
-  const long kslice = ((ksteps + S - 1) / S) * BK;
-  S = (K + kslice - 1) / kslice;  // actual slices after rounding
-
-  torch::Tensor part;
-  float* part_ptr = nullptr;
-  if (S > 1) {
-    part = torch::empty({S, M, N},
-                        A.options().dtype(at::kFloat));
-    part_ptr = part.data_ptr<float>();
-  }
-
-  dim3 grid((unsigned)tiles, (unsigned)S);
-  const int vecA = ta ? (M % 8 == 0) : (K % 8 == 0);
-  const int vecB = tb ? (K % 8 == 0) : (N % 8 == 0);
-
-  auto launch = [&](auto bm, auto bn, auto wr, auto wc) {
-    constexpr int BMv = decltype(bm)::value, BNv = decltype(bn)::value;
-    constexpr int WRv = decltype(wr)::value, WCv = decltype(wc)::value;
-    dim3 block(WRv * WCv * 64);
-    const int sm = (int)store;
-    if (!ta && !tb)
-      hipLaunchKernelGGL((gemm_kernel<BMv, BNv, WRv, WCv, false, false>),
-                         grid, block, 0, cur_stream(), a, b, c, part_ptr, bs,
-                         M, N, K, kslice, relu, sm, ohw, vecA, vecB,
-                         ConvShape{});
-    else if (!ta && tb)
-      hipLaunchKernelGGL((gemm_kernel<BMv, BNv, WRv, WCv, false, true>),
-                         grid, block, 0, cur_stream(), a, b, c, part_ptr, bs,
-                         M, N, K, kslice, relu, sm, ohw, vecA, vecB,
-                         ConvShape{});
-    else if (ta && !tb)
-      hipLaunchKernelGGL((gemm_kernel<BMv, BNv, WRv, WCv, true, false>),
-                         grid, block, 0, cur_stream(), a, b, c, part_ptr, bs,
-                         M, N, K, kslice, relu, sm, ohw, vecA, vecB,
-                         ConvShape{});
+    if (ta) { At = transpose_bf16(A); a = (const bf16*)At.data_ptr(); }
+    if (!tb) { Bt = transpose_bf16(B); b = (const bf16*)Bt.data_ptr(); }
+    const BnStatsPtrs st = alloc_bn_stats(
+        bn_stats, p.S == 1 && store == EpStore::kPlain, p, M, N, A);
+    if (p.path == GemmPath::kGemm8p)
+      hipLaunchKernelGGL(gemm8p_kernel, grid, dim3(512), 0, cur_stream(), a,
+                         b, c, part.ptr, bs, M, N, K, p.kslice, relu_i,
+                         st.sum, st.sq);
     else
-      hipLaunchKernelGGL((gemm_kernel<BMv, BNv, WRv, WCv, true, true>),
-                         grid, block, 0, cur_stream(), a, b, c, part_ptr, bs,
-                         M, N, K, kslice, relu, sm, ohw, vecA, vecB,
-                         ConvShape{});
-  };
-
-  using c32 = std::integral_constant<int, 32>;
-  using c64 = std::integral_constant<int, 64>;
-  using c128 = std::integral_constant<int, 128>;
-  using c1 = std::integral_constant<int, 1>;
-  using c2 = std::integral_constant<int, 2>;
-  using c4 = std::integral_constant<int, 4>;
-
-  const int key = t.bm * 1000 + t.bn;
-  switch (key) {
-    case 128128: launch(c128{}, c128{}, c2{}, c2{}); break;
-    case 128064: launch(c128{}, c64{}, c2{}, c2{}); break;
-    case 128032: launch(c128{}, c32{}, c2{}, c2{}); break;
-    case  64128: launch(c64{}, c128{}, c2{}, c2{}); break;
-    case  64064: launch(c64{}, c64{}, c2{}, c2{}); break;
-    case  64032: launch(c64{}, c32{}, c2{}, c2{}); break;
-    case  32128: launch(c32{}, c128{}, c1{}, c4{}); break;
-    case  32064: launch(c32{}, c64{}, c1{}, c4{}); break;
-    case  32032: launch(c32{}, c32{}, c2{}, c1{}); break;
-    default: TORCH_CHECK(false, "no tile config for ", t.bm, "x", t.bn);
+      dispatch_dbuf(p, [&](auto bm, auto bn) {
+        hipLaunchKernelGGL(
+            (gemm256_kernel<decltype(bm)::value, decltype(bn)::value>), grid,
+            dim3(512), 0, cur_stream(), a, b, c, part.ptr, bs, M, N, K,
+            p.kslice, relu_i, sm, ohw, ConvShape{}, st.sum, st.sq);
+      });
   }
   HIP_CHECK(hipGetLastError());
+  if (p.S > 1)
+    launch_splitk_reduce(part.ptr, p.S, M, N, c, bs, relu_i, store, ohw);
+}
 
-  if (S > 1)
-    launch_splitk_reduce(part_ptr, S, M, N, c, bs, relu ? 1 : 0, store,
-                         ohw);
+// Route query: the plan gemm_raw's launch takes for this shape (path,
+// bm, bn, S, kslice). Allocates and launches nothing.
+PlanRow gemm_plan_route(long M, long N, long K, bool ta, bool tb) {
+  return plan_row(plan_dense(M, N, K, ta, tb, true, false,
+                             wgrad_small_gate()));
+}
+
+std::tuple<long, long, long, long> colsum_geom_query(long M, long N) {
+  const ColsumGeom g = colsum_geom(M, N);
+  return {g.G, g.cblocks, g.rows, g.chunks};
 }
 
 torch::Tensor colsum_bf16(const torch::Tensor& X) {
   CHECK_GPU(X); CHECK_CONTIG(X);
   long M = X.size(0), N = X.size(1);
   auto out = torch::empty({N}, X.options());
-  int G = 1;
-  while (G * 2 <= std::min<long>(N / 8, 256)) G *= 2;
-  const int cblocks = (N % 8 == 0) ? (int)ceil_div(N / 8, (long)G)
-                                   : (int)ceil_div(N, (long)32);
-  const long target =
-      std::max<long>(1, std::min<long>(768 / std::max(cblocks, 1), 256));
-  const long rows = std::max<long>(64, (M + target - 1) / target);
-  const int chunks = (int)((M + rows - 1) / rows);
-  auto part = torch::empty({chunks, N}, X.options().dtype(at::kFloat));
+  const ColsumGeom g = colsum_geom(M, N);
+  auto part = torch::empty({g.chunks, N}, X.options().dtype(at::kFloat));
   if (N % 8 == 0) {
-    hipLaunchKernelGGL(colsum_part_vec_kernel, dim3(cblocks, chunks),
+    hipLaunchKernelGGL(colsum_part_vec_kernel, dim3(g.cblocks, g.chunks),
                        dim3(256), 0, cur_stream(),
-                       (const bf16*)X.data_ptr(), M, N, G, rows,
+                       (const bf16*)X.data_ptr(), M, N, g.G, g.rows,
                        part.data_ptr<float>());
   } else {
-    hipLaunchKernelGGL(colsum_part_kernel, dim3(cblocks, chunks),
+    hipLaunchKernelGGL(colsum_part_kernel, dim3(g.cblocks, g.chunks),
                        dim3(256), 0, cur_stream(),
-                       (const bf16*)X.data_ptr(), M, N, rows,
+                       (const bf16*)X.data_ptr(), M, N, g.rows,
                        part.data_ptr<float>());
   }
   HIP_CHECK(hipGetLastError());
-  if (N % 4 == 0) {
-    int G4 = 1;  // <= 16 so every block keeps >= 16 chunk-lanes
-    while (G4 * 2 <= std::min<long>(N / 4, 16)) G4 *= 2;
-    hipLaunchKernelGGL(colsum_final_vec_kernel,
-                       dim3(ceil_div(N / 4, (long)G4)), dim3(256), 0,
-                       cur_stream(), part.data_ptr<float>(), chunks, N, G4,
-                       (bf16*)out.data_ptr());
-  } else {
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(ceil_div(N, 32)),
-                       dim3(256), 0, cur_stream(), part.data_ptr<float>(),
-                       chunks, N, (bf16*)out.data_ptr());
-  }
-  HIP_CHECK(hipGetLastError());
+  launch_colsum_final(part.data_ptr<float>(), g.chunks, N,
+                      (bf16*)out.data_ptr());
   return out;
 }
 
@@ -2235,32 +2158,8 @@ torch::Tensor colsum_bf16(const torch::Tensor& X) {
 // pooled conv backward): out[n] = bf16(sum over chunks of part[k][n]),
 // the same kernels and fixed trees colsum_bf16 ends with.
 void colsum_finalize(const torch::Tensor& part, torch::Tensor& out) {
-  const int chunks = (int)part.size(0);
-  const long N = part.size(1);
-  if (N % 4 == 0) {
-    int G4 = 1;
-    while (G4 * 2 <= std::min<long>(N / 4, 16)) G4 *= 2;
-    hipLaunchKernelGGL(colsum_final_vec_kernel,
-                       dim3(ceil_div(N / 4, (long)G4)), dim3(256), 0,
-                       cur_stream(), part.data_ptr<float>(), chunks, N, G4,
-                       (bf16*)out.data_ptr());
-  } else {
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(ceil_div(N, 32)),
-                       dim3(256), 0, cur_stream(), part.data_ptr<float>(),
-                       chunks, N, (bf16*)out.data_ptr());
-  }
-  HIP_CHECK(hipGetLastError());
-}
-
-// Row-chunk length colsum_bf16 uses for an [M, N] bf16 matrix (N % 8
-// == 0): a few waves per SIMD across the 256 CUs, from the shape alone.
-long colsum_chunk_rows(long M, long N) {
-  int G = 1;
-  while (G * 2 <= std::min<long>(N / 8, 256)) G *= 2;
-  const int cblocks = (int)ceil_div(N / 8, (long)G);
-  const long target =
-      std::max<long>(1, std::min<long>(768 / std::max(cblocks, 1), 256));
-  return std::max<long>(64, (M + target - 1) / target);
+  launch_colsum_final(part.data_ptr<float>(), (int)part.size(0),
+                      part.size(1), (bf16*)out.data_ptr());
 }
 
 // Fused relu backward + bias-grad column sum over dy viewed [M, N]
@@ -2276,31 +2175,43 @@ std::tuple<torch::Tensor, torch::Tensor> relu_bwd_colsum(
   TORCH_CHECK(y.numel() == dy.numel());
   auto dx = torch::empty_like(dy);
   auto out = torch::empty({N}, dy.options());
-  int G = 1;
-  while (G * 2 <= std::min<long>(N / 8, 256)) G *= 2;
-  const int cblocks = (int)ceil_div(N / 8, (long)G);
-  const long target =
-      std::max<long>(1, std::min<long>(768 / std::max(cblocks, 1), 256));
-  const long rows = std::max<long>(64, (M + target - 1) / target);
-  const int chunks = (int)((M + rows - 1) / rows);
-  auto part = torch::empty({chunks, N}, dy.options().dtype(at::kFloat));
+  const ColsumGeom g = colsum_geom(M, N);
+  auto part = torch::empty({g.chunks, N}, dy.options().dtype(at::kFloat));
   hipLaunchKernelGGL(relu_bwd_colsum_part_vec_kernel,
-                     dim3(cblocks, chunks), dim3(256), 0, cur_stream(),
+                     dim3(g.cblocks, g.chunks), dim3(256), 0, cur_stream(),
                      (const bf16*)y.data_ptr(), (const bf16*)dy.data_ptr(),
-                     (bf16*)dx.data_ptr(), M, N, G, rows,
+                     (bf16*)dx.data_ptr(), M, N, g.G, g.rows,
                      part.data_ptr<float>());
   HIP_CHECK(hipGetLastError());
-  int G4 = 1;
-  while (G4 * 2 <= std::min<long>(N / 4, 16)) G4 *= 2;
-  hipLaunchKernelGGL(colsum_final_vec_kernel,
-                     dim3(ceil_div(N / 4, (long)G4)), dim3(256), 0,
-                     cur_stream(), part.data_ptr<float>(), chunks, N, G4,
-                     (bf16*)out.data_ptr());
-  HIP_CHECK(hipGetLastError());
+  launch_colsum_final(part.data_ptr<float>(), g.chunks, N,
+                      (bf16*)out.data_ptr());
   return {dx, out};
 }
 
-// Raw GEMM entry (benchmark/ablation): C[M,N] = op(A) @ op(B).
+// Plan of an implicit-GEMM conv entry; path kNone = the entry declines
+// the shape (its caller materializes col / dcol instead). The launchers
+// and conv_plan_route both ask here. The pooled forward gets the plain
+// forward's plan (M counts the same rows, window-major), so every
+// output element sees the same accumulation order and the fused result
+// is bitwise conv-then-pool.
+GemmPlan gemm_conv_plan(ConvEntry e, const ConvShape& sh) {
+  const GemmDims d = conv_gemm_dims(e, sh);
+  if (e == ConvEntry::kWgrad)
+    // always the small-tile split-K shape (M' = Kout is small, K' = M
+    // is huge)
+    return sh.C % 8 == 0 ? plan_small(d.M, d.N, d.K) : GemmPlan{};
+  const int inner = e == ConvEntry::kDgrad ? sh.Kout : sh.C;  // granule dim
+  if (inner % 8 != 0 || d.M < 48) return {};
+  // fused pool: double-buffered wide-N forward only
+  if (e == ConvEntry::kFwdPool &&
+      (d.N % 64 != 0 || d.N < 64 || sh.OH % 2 != 0 || sh.OW % 2 != 0))
+    return {};
+  return plan_conv(d.M, d.N, d.K, narrow_dbuf_gate());
+}
+
+namespace {
+
+// CMODE 1: forward (optionally pooled), CMODE 2: dgrad.
 template <int CMODE>
 bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
                         torch::Tensor& y, const ConvShape& sh,
@@ -2308,244 +2219,75 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
                         std::pair<torch::Tensor, torch::Tensor>* bn_stats
                         = nullptr, bool pool = false,
                         uint8_t* pool_idx = nullptr) {
-  // CMODE 1 (fwd):   y[M=N*OH*OW][Kout], K = R*S*C, A = x gather
-  // CMODE 2 (dgrad): y[M=N*H*W][C],      K = R*S*Kout, A = dy gather
-  const long M = CMODE == 1 ? sh.M() : (long)sh.N * sh.H * sh.W;
-  const long N = CMODE == 1 ? sh.Kout : sh.C;
-  const long K = CMODE == 1 ? sh.RSC() : (long)sh.R * sh.S * sh.Kout;
-  const int inner = CMODE == 1 ? sh.C : sh.Kout;  // granule dimension
-  if (inner % 8 != 0 || M < 48) return false;
-  if (pool && (CMODE != 1 || N % 64 != 0 || N < 64 || sh.OH % 2 != 0 ||
-               sh.OW % 2 != 0 || bn_stats))
-    return false;  // fused pool: double-buffered wide-N forward only
-  if (N % 64 != 0 || N < 64) {
-    // narrow-N convs (ResNet-20's Kout 16/32): implicit gather in the
-    // synchronous small-tile kernel — the col read it replaces is the
-    // traffic bound there (col is R*S times the activation).
-    //
-    // Double-buffered narrow-BN route (default OFF — measured
-    // negative): gemm256_kernel's BN==32 wave grid register-stages
-    // K-step t+2 while the MFMAs of t run, the theory being that the
-    // sync kernel serializes gather-stage -> barrier -> MFMA at ~10x
-    // the traffic bound. A/B on hardware (gpurun_out/r20_kd*.json):
-    // ResNet-20 protocol round 67.5 ms dbuf vs 64.0 sync, FEMNIST 9.05
-    // vs 9.07 — the sync kernel's 256-thread blocks oversubscribe each
-    // CU with multiple blocks, which already hides the stage latency;
-    // the 512-thread dbuf blocks halve that block-level parallelism
-    // and its staging VALU count is no lower (the real bound —
-    // MemUnitStalled ~0, profiles/r02_pmc_femnist.md). Kept behind
-    // BFLC_NARROW_DBUF=1 as the documented experiment.
-    static const bool narrow_dbuf = [] {
-      const char* e = getenv("BFLC_NARROW_DBUF");
-      return e && e[0] == '1';
-    }();
-    if (narrow_dbuf && N <= 32 && M >= 8192) {
-      const int bm2 = M >= 32768 ? 128 : 64;
-      const long tiles = ((M + bm2 - 1) / bm2) * ((N + 31) / 32);
-      const long ksteps64 = (K + BK2 - 1) / BK2;
-      const double tf = bm2 == 128 ? 450.0e12 : 250.0e12;
-      long S = pick_splitk(M, N, K, tiles, ksteps64, 256, tf);
-      const long kslice = ((ksteps64 + S - 1) / S) * BK2;
-      S = (K + kslice - 1) / kslice;
-      torch::Tensor part;
-      float* part_ptr = nullptr;
-      if (S > 1) {
-        part = torch::empty({S, M, N}, x.options().dtype(at::kFloat));
-        part_ptr = part.data_ptr<float>();
-      }
-      const bf16* a = (const bf16*)x.data_ptr();
-      const bf16* b = (const bf16*)w2.data_ptr();
-      bf16* c = (bf16*)y.data_ptr();
-      const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
-      dim3 grid((unsigned)tiles, (unsigned)S);
-      dim3 block(512);
-      float* stp = nullptr;
-      float* stq = nullptr;
-      if (bn_stats && CMODE == 1 && S == 1) {
-        const long chunks = (M + bm2 - 1) / bm2;
-        bn_stats->first = torch::empty({chunks, N},
-                                       x.options().dtype(at::kFloat));
-        bn_stats->second = torch::empty({chunks, N},
-                                        x.options().dtype(at::kFloat));
-        stp = bn_stats->first.data_ptr<float>();
-        stq = bn_stats->second.data_ptr<float>();
-      }
-      if (bm2 == 128) {
-        hipLaunchKernelGGL((gemm256_kernel<128, 32, CMODE>), grid, block,
-                           0, cur_stream(), a, b, c, part_ptr, bs, M, N,
-                           K, kslice, relu ? 1 : 0, (int)EpStore::kPlain,
-                           0, sh, stp, stq);
-      } else {
-        hipLaunchKernelGGL((gemm256_kernel<64, 32, CMODE>), grid, block,
-                           0, cur_stream(), a, b, c, part_ptr, bs, M, N,
-                           K, kslice, relu ? 1 : 0, (int)EpStore::kPlain,
-                           0, sh, stp, stq);
-      }
-      HIP_CHECK(hipGetLastError());
-      if (S > 1)
-        launch_splitk_reduce(part_ptr, S, M, N, c, bs, relu ? 1 : 0,
-                             EpStore::kPlain, 0);
-      return true;
-    }
-    const bf16* a = (const bf16*)x.data_ptr();
-    const bf16* b = (const bf16*)w2.data_ptr();
-    bf16* c = (bf16*)y.data_ptr();
-    const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
-    const TileCfg t = pick_tile(M, N);
-    const long tiles = ((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
-    const long ksteps = (K + BK - 1) / BK;
-    long S = pick_splitk(M, N, K, tiles, ksteps, 512, 150.0e12);
-    const long kslice = ((ksteps + S - 1) / S) * BK;
-    S = (K + kslice - 1) / kslice;
-    torch::Tensor part;
-    float* part_ptr = nullptr;
-    if (S > 1) {
-      part = torch::empty({S, M, N}, x.options().dtype(at::kFloat));
-      part_ptr = part.data_ptr<float>();
-    }
-    dim3 grid((unsigned)tiles, (unsigned)S);
-    float* stp = nullptr;
-    float* stq = nullptr;
-    if (bn_stats && CMODE == 1 && S == 1) {
-      const long chunks = (M + t.bm - 1) / t.bm;
-      bn_stats->first = torch::empty({chunks, N},
-                                     x.options().dtype(at::kFloat));
-      bn_stats->second = torch::empty({chunks, N},
-                                      x.options().dtype(at::kFloat));
-      stp = bn_stats->first.data_ptr<float>();
-      stq = bn_stats->second.data_ptr<float>();
-    }
-    auto launchcc = [&](auto bm, auto bn, auto wr, auto wc) {
-      constexpr int BMv = decltype(bm)::value, BNv = decltype(bn)::value;
-      constexpr int WRv = decltype(wr)::value, WCv = decltype(wc)::value;
-      dim3 block(WRv * WCv * 64);
-      hipLaunchKernelGGL(
-          (gemm_kernel<BMv, BNv, WRv, WCv, false, true, CMODE>), grid,
-          block, 0, cur_stream(), a, b, c, part_ptr, bs, M, N, K, kslice,
-          relu ? 1 : 0, (int)EpStore::kPlain, 0, 0, 1, sh, stp, stq);
-    };
-    using c32 = std::integral_constant<int, 32>;
-    using c64 = std::integral_constant<int, 64>;
-    using c128 = std::integral_constant<int, 128>;
-    using c1 = std::integral_constant<int, 1>;
-    using c2 = std::integral_constant<int, 2>;
-    using c4 = std::integral_constant<int, 4>;
-    switch (t.bm * 1000 + t.bn) {
-      case 128128: launchcc(c128{}, c128{}, c2{}, c2{}); break;
-      case 128064: launchcc(c128{}, c64{}, c2{}, c2{}); break;
-      case 128032: launchcc(c128{}, c32{}, c2{}, c2{}); break;
-      case  64128: launchcc(c64{}, c128{}, c2{}, c2{}); break;
-      case  64064: launchcc(c64{}, c64{}, c2{}, c2{}); break;
-      case  64032: launchcc(c64{}, c32{}, c2{}, c2{}); break;
-      case  32128: launchcc(c32{}, c128{}, c1{}, c4{}); break;
-      case  32064: launchcc(c32{}, c64{}, c1{}, c4{}); break;
-      case  32032: launchcc(c32{}, c32{}, c2{}, c1{}); break;
-      default: return false;
-    }
-    HIP_CHECK(hipGetLastError());
-    if (S > 1)
-      launch_splitk_reduce(part_ptr, S, M, N, c, bs, relu ? 1 : 0,
-                           EpStore::kPlain, 0);
-    return true;
-  }
-  const long ksteps64 = (K + BK2 - 1) / BK2;
-  const int bn2 = (N % 256 == 0) ? 256 : (N % 128 == 0 ? 128 : 64);
-  const long ntn2 = (N + bn2 - 1) / bn2;
-  int bm2 = 256;
-  long S = 1;
-  {
-    double best_t = 1e30;
-    const double bn_pen = bn2 >= 128 ? 1.0 : 0.75;
-    for (int bm : (bn2 == 64 ? std::initializer_list<int>{128, 64}
-                               : std::initializer_list<int>{256, 128, 64})) {
-      const double tf = (bm == 256 ? 800.0e12
-                                   : (bm == 128 ? 600.0e12 : 320.0e12)) *
-                        bn_pen;
-      const long tiles_c = ((M + bm - 1) / bm) * ntn2;
-      double t;
-      const long ss = pick_splitk(M, N, K, tiles_c, ksteps64, 256, tf, &t);
-      if (t < best_t) { best_t = t; bm2 = bm; S = ss; }
-    }
-  }
-  const long tiles = ((M + bm2 - 1) / bm2) * ntn2;
-  const long kslice = ((ksteps64 + S - 1) / S) * BK2;
-  S = (K + kslice - 1) / kslice;
-  torch::Tensor part;
-  float* part_ptr = nullptr;
-  if (S > 1) {
-    part = torch::empty({S, M, N}, x.options().dtype(at::kFloat));
-    part_ptr = part.data_ptr<float>();
-  }
+  const ConvEntry e = CMODE == 2 ? ConvEntry::kDgrad
+                                 : (pool ? ConvEntry::kFwdPool
+                                         : ConvEntry::kFwd);
+  const GemmPlan p = gemm_conv_plan(e, sh);
+  if (p.path == GemmPath::kNone || (pool && bn_stats)) return false;
+  const GemmDims d = conv_gemm_dims(e, sh);
+  const long M = d.M, N = d.N, K = d.K;
   const bf16* a = (const bf16*)x.data_ptr();
   const bf16* b = (const bf16*)w2.data_ptr();
   bf16* c = (bf16*)y.data_ptr();
   const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
-  dim3 grid((unsigned)tiles, (unsigned)S);
-  dim3 block(512);
-  float* stp = nullptr;
-  float* stq = nullptr;
-  if (bn_stats && CMODE == 1 && S == 1) {
-    const long chunks = (M + bm2 - 1) / bm2;
-    bn_stats->first = torch::empty({chunks, N},
-                                   x.options().dtype(at::kFloat));
-    bn_stats->second = torch::empty({chunks, N},
-                                    x.options().dtype(at::kFloat));
-    stp = bn_stats->first.data_ptr<float>();
-    stq = bn_stats->second.data_ptr<float>();
-  }
-  // pool: same tile / split-K choice as the plain forward of this
-  // shape (M counts the same rows, window-major), so every output
-  // element sees the same accumulation order and the fused result is
-  // bitwise conv-then-pool.
-  auto launchc = [&](auto bmv, auto bnv) {
-    if constexpr (CMODE == 1) {
-      // split-K launches pool (and pick the argmax) in the reduce
-      if (pool && pool_idx && S == 1) {
-        hipLaunchKernelGGL(
-            (gemm256_kernel<decltype(bmv)::value, decltype(bnv)::value, 1,
-                            2>),
-            grid, block, 0, cur_stream(), a, b, c, part_ptr, bs, M, N, K,
-            kslice, relu ? 1 : 0, (int)EpStore::kPlain, 0, sh, stp, stq,
-            pool_idx);
-        return;
+  const int relu_i = relu ? 1 : 0, plain = (int)EpStore::kPlain;
+  const SplitKPart part = alloc_splitk_part(p, M, N, x);
+  const dim3 grid((unsigned)p.tiles, (unsigned)p.S);
+  const BnStatsPtrs st =
+      alloc_bn_stats(bn_stats, CMODE == 1 && p.S == 1, p, M, N, x);
+  if (p.path == GemmPath::kSmall) {
+    dispatch_small(p, [&](auto bm, auto bn, auto wr, auto wc) {
+      constexpr int BMv = decltype(bm)::value, BNv = decltype(bn)::value;
+      constexpr int WRv = decltype(wr)::value, WCv = decltype(wc)::value;
+      hipLaunchKernelGGL(
+          (gemm_kernel<BMv, BNv, WRv, WCv, false, true, CMODE>), grid,
+          dim3(WRv * WCv * 64), 0, cur_stream(), a, b, c, part.ptr, bs, M,
+          N, K, p.kslice, relu_i, plain, 0, 0, 1, sh, st.sum, st.sq);
+    });
+  } else if (p.bn == 32) {  // the BFLC_NARROW_DBUF experiment
+    auto launchn = [&](auto bm) {
+      hipLaunchKernelGGL((gemm256_kernel<decltype(bm)::value, 32, CMODE>),
+                         grid, dim3(512), 0, cur_stream(), a, b, c, part.ptr,
+                         bs, M, N, K, p.kslice, relu_i, plain, 0, sh,
+                         st.sum, st.sq);
+    };
+    if (p.bm == 128) launchn(ic<128>{});
+    else launchn(ic<64>{});
+  } else {
+    dispatch_dbuf(p, [&](auto bm, auto bn) {
+      constexpr int BMv = decltype(bm)::value, BNv = decltype(bn)::value;
+      if constexpr (CMODE == 1) {
+        // split-K launches pool (and pick the argmax) in the reduce
+        if (pool && pool_idx && p.S == 1) {
+          hipLaunchKernelGGL((gemm256_kernel<BMv, BNv, 1, 2>), grid,
+                             dim3(512), 0, cur_stream(), a, b, c, part.ptr,
+                             bs, M, N, K, p.kslice, relu_i, plain, 0, sh,
+                             st.sum, st.sq, pool_idx);
+          return;
+        }
+        if (pool) {
+          hipLaunchKernelGGL((gemm256_kernel<BMv, BNv, 1, 1>), grid,
+                             dim3(512), 0, cur_stream(), a, b, c, part.ptr,
+                             bs, M, N, K, p.kslice, relu_i, plain, 0, sh,
+                             st.sum, st.sq);
+          return;
+        }
       }
-      if (pool) {
-        hipLaunchKernelGGL(
-            (gemm256_kernel<decltype(bmv)::value, decltype(bnv)::value, 1,
-                            1>),
-            grid, block, 0, cur_stream(), a, b, c, part_ptr, bs, M, N, K,
-            kslice, relu ? 1 : 0, (int)EpStore::kPlain, 0, sh, stp, stq);
-        return;
-      }
-    }
-    hipLaunchKernelGGL(
-        (gemm256_kernel<decltype(bmv)::value, decltype(bnv)::value, CMODE>),
-        grid, block, 0, cur_stream(), a, b, c, part_ptr, bs, M, N, K,
-        kslice, relu ? 1 : 0, (int)EpStore::kPlain, 0, sh, stp, stq);
-  };
-  using c64i = std::integral_constant<int, 64>;
-  using c128i = std::integral_constant<int, 128>;
-  using c256i = std::integral_constant<int, 256>;
-  switch (bm2 * 1000 + bn2) {
-    case 256256: launchc(c256i{}, c256i{}); break;
-    case 256128: launchc(c256i{}, c128i{}); break;
-    case 256064: launchc(c256i{}, c64i{}); break;
-    case 128256: launchc(c128i{}, c256i{}); break;
-    case 128128: launchc(c128i{}, c128i{}); break;
-    case 128064: launchc(c128i{}, c64i{}); break;
-    case  64256: launchc(c64i{}, c256i{}); break;
-    case  64128: launchc(c64i{}, c128i{}); break;
-    case  64064: launchc(c64i{}, c64i{}); break;
+      hipLaunchKernelGGL((gemm256_kernel<BMv, BNv, CMODE>), grid, dim3(512),
+                         0, cur_stream(), a, b, c, part.ptr, bs, M, N, K,
+                         p.kslice, relu_i, plain, 0, sh, st.sum, st.sq);
+    });
   }
   HIP_CHECK(hipGetLastError());
-  if (S > 1 && pool)
-    launch_splitk_reduce_pool(part_ptr, S, M, N, c, bs, relu ? 1 : 0,
-                              pool_idx);
-  else if (S > 1)
-    launch_splitk_reduce(part_ptr, S, M, N, c, bs, relu ? 1 : 0,
+  if (p.S > 1 && pool)
+    launch_splitk_reduce_pool(part.ptr, p.S, M, N, c, bs, relu_i, pool_idx);
+  else if (p.S > 1)
+    launch_splitk_reduce(part.ptr, p.S, M, N, c, bs, relu_i,
                          EpStore::kPlain, 0);
   return true;
 }
+
+}  // namespace
 
 bool gemm_conv_fwd_raw(const torch::Tensor& x, const torch::Tensor& w2,
                        torch::Tensor& y, const ConvShape& sh,
@@ -2555,15 +2297,13 @@ bool gemm_conv_fwd_raw(const torch::Tensor& x, const torch::Tensor& w2,
 }
 
 bool gemm_conv_fwd_pool_eligible(const ConvShape& sh) {
-  return sh.C % 8 == 0 && sh.M() >= 48 && sh.Kout % 64 == 0 &&
-         sh.Kout >= 64 && sh.OH % 2 == 0 && sh.OW % 2 == 0;
+  return gemm_conv_plan(ConvEntry::kFwdPool, sh).path != GemmPath::kNone;
 }
 
 bool gemm_conv_fwd_pool_raw(const torch::Tensor& x, const torch::Tensor& w2,
                             torch::Tensor& y, const ConvShape& sh,
                             const torch::Tensor* bias, bool relu,
                             uint8_t* idx) {
-  if (!gemm_conv_fwd_pool_eligible(sh)) return false;
   return conv_implicit_gemm<1>(x, w2, y, sh, bias, relu, nullptr, true, idx);
 }
 
@@ -2574,28 +2314,17 @@ bool gemm_conv_dgrad_raw(const torch::Tensor& dy, const torch::Tensor& wrot2,
 
 // wgrad: dW[Kout, RSC] = dy2^T @ implicit-col(x). A = dy2 [M, Kout]
 // through the TA scatter staging, B = x through the CMODE-3 gather —
-// the col matrix never exists. Always the small-tile split-K shape
-// (M' = Kout is small, K' = M is huge).
+// the col matrix never exists.
 bool gemm_conv_wgrad_raw(const torch::Tensor& dy2, const torch::Tensor& x,
                          torch::Tensor& dw, const ConvShape& sh) {
-  if (sh.C % 8 != 0) return false;
-  const long M = sh.Kout, N = sh.RSC(), K = sh.M();
+  const GemmPlan p = gemm_conv_plan(ConvEntry::kWgrad, sh);
+  if (p.path == GemmPath::kNone) return false;
+  const GemmDims d = conv_gemm_dims(ConvEntry::kWgrad, sh);
   const bf16* a = (const bf16*)dy2.data_ptr();
   const bf16* b = (const bf16*)x.data_ptr();
   bf16* c = (bf16*)dw.data_ptr();
-  const TileCfg t = pick_tile(M, N);
-  const long tiles = ((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
-  const long ksteps = (K + BK - 1) / BK;
-  long S = pick_splitk(M, N, K, tiles, ksteps, 512, 150.0e12);
-  const long kslice = ((ksteps + S - 1) / S) * BK;
-  S = (K + kslice - 1) / kslice;
-  torch::Tensor part;
-  float* part_ptr = nullptr;
-  if (S > 1) {
-    part = torch::empty({S, M, N}, x.options().dtype(at::kFloat));
-    part_ptr = part.data_ptr<float>();
-  }
-  dim3 grid((unsigned)tiles, (unsigned)S);
+  const SplitKPart part = alloc_splitk_part(p, d.M, d.N, x);
+  const dim3 grid((unsigned)p.tiles, (unsigned)p.S);
   // k-pair scatter staging (CMODE 4): each LDS slot owns two adjacent
   // k's of one n-granule, halving ds_write instructions in the staging
   // loop. Default ON since the round-2 A/B on MI355X: every wgrad-heavy
@@ -2607,46 +2336,25 @@ bool gemm_conv_wgrad_raw(const torch::Tensor& dy2, const torch::Tensor& x,
     const char* e = getenv("BFLC_WGRAD_KPAIR");
     return !e || atoi(e) != 0;
   }();
-  auto launchw = [&](auto bm, auto bn, auto wr, auto wc) {
+  dispatch_small(p, [&](auto bm, auto bn, auto wr, auto wc) {
     constexpr int BMv = decltype(bm)::value, BNv = decltype(bn)::value;
     constexpr int WRv = decltype(wr)::value, WCv = decltype(wc)::value;
-    dim3 block(WRv * WCv * 64);
-    if (kpair)
+    dispatch_bool(kpair, [&](auto kp) {
+      constexpr int CM = decltype(kp)::value ? 4 : 3;
       hipLaunchKernelGGL(
-          (gemm_kernel<BMv, BNv, WRv, WCv, true, false, 4>), grid, block,
-          0, cur_stream(), a, b, c, part_ptr, nullptr, M, N, K, kslice, 0,
-          (int)EpStore::kPlain, 0, 1, 0, sh);
-    else
-      hipLaunchKernelGGL(
-          (gemm_kernel<BMv, BNv, WRv, WCv, true, false, 3>), grid, block,
-          0, cur_stream(), a, b, c, part_ptr, nullptr, M, N, K, kslice, 0,
-          (int)EpStore::kPlain, 0, 1, 0, sh);
-  };
-  using c32 = std::integral_constant<int, 32>;
-  using c64 = std::integral_constant<int, 64>;
-  using c128 = std::integral_constant<int, 128>;
-  using c1 = std::integral_constant<int, 1>;
-  using c2 = std::integral_constant<int, 2>;
-  using c4 = std::integral_constant<int, 4>;
-  switch (t.bm * 1000 + t.bn) {
-    case 128128: launchw(c128{}, c128{}, c2{}, c2{}); break;
-    case 128064: launchw(c128{}, c64{}, c2{}, c2{}); break;
-    case 128032: launchw(c128{}, c32{}, c2{}, c2{}); break;
-    case  64128: launchw(c64{}, c128{}, c2{}, c2{}); break;
-    case  64064: launchw(c64{}, c64{}, c2{}, c2{}); break;
-    case  64032: launchw(c64{}, c32{}, c2{}, c2{}); break;
-    case  32128: launchw(c32{}, c128{}, c1{}, c4{}); break;
-    case  32064: launchw(c32{}, c64{}, c1{}, c4{}); break;
-    case  32032: launchw(c32{}, c32{}, c2{}, c1{}); break;
-    default: return false;
-  }
+          (gemm_kernel<BMv, BNv, WRv, WCv, true, false, CM>), grid,
+          dim3(WRv * WCv * 64), 0, cur_stream(), a, b, c, part.ptr, nullptr,
+          d.M, d.N, d.K, p.kslice, 0, (int)EpStore::kPlain, 0, 1, 0, sh);
+    });
+  });
   HIP_CHECK(hipGetLastError());
-  if (S > 1)
-    launch_splitk_reduce(part_ptr, S, M, N, c, nullptr, 0,
+  if (p.S > 1)
+    launch_splitk_reduce(part.ptr, p.S, d.M, d.N, c, nullptr, 0,
                          EpStore::kPlain, 0);
   return true;
 }
 
+// Raw GEMM entry (benchmark/ablation): C[M,N] = op(A) @ op(B).
 torch::Tensor gemm_raw(torch::Tensor A, torch::Tensor B, bool ta, bool tb) {
   CHECK_GPU(A); CHECK_CONTIG(A); CHECK_CONTIG(B);
   const long M = ta ? A.size(1) : A.size(0);
