@@ -185,7 +185,23 @@ def main():
         out[f"train.{name}.unpool_relu_colsum"] = timeit(
             lambda: h_ops.pool_relu_bwd_colsum(yp, idx, dy, full),
             args.iters)
+        # what bwd_pooled runs underneath for a thin first layer
+        # (BFLC_THIN_FUSED_WGRAD), next to both of its implementations
+        out[f"train.{name}.bwd_pooled_impl"] = h_ops.thin_pool_wgrad_impl(
+            list(x.shape), list(w.shape), stride, pad, want_dx)
+
+        def materialized_chain():
+            dyf, db = h_ops.pool_relu_bwd_colsum(yp, idx, dy, full)
+            return h_ops.conv2d_bwd(x, w, dyf, stride, pad, None, False,
+                                    want_dx)
+
+        out[f"train.{name}.bwd_materialized_chain"] = timeit(
+            materialized_chain, args.iters)
         if not want_dx:
+            out[f"train.{name}.thin_fused_wgrad"] = timeit(
+                lambda: h_ops.thin_conv_pool_wgrad_fused(x, yp, idx, dy,
+                                                         stride, pad),
+                args.iters)
             out[f"train.{name}.thin_direct_wgrad"] = timeit(
                 lambda: h_ops.thin_conv_pool_wgrad(x, yp, idx, dy, stride,
                                                    pad), args.iters)

@@ -307,8 +307,10 @@ class _ConvReluPoolFn(torch.autograd.Function):
     epilogue and also emits the u8 argmax plane; only (x, w, y_pooled,
     idx) are saved — the full-resolution activation never exists. The
     backward unpools, ReLU-masks by y_pooled > 0 and sums db in one
-    pass, then runs the unchanged conv backward: every gradient is
-    bitwise the two-op path's. With direct_wgrad (BFLC_THIN_DIRECT_WGRAD
+    pass, then runs the unchanged conv backward (for a thin first layer
+    the same MFMA chains fed straight from the pooled tensors, see
+    thin_conv_pool_wgrad_fused): every gradient is bitwise the two-op
+    path's. With direct_wgrad (BFLC_THIN_DIRECT_WGRAD
     =1) a thin first layer goes straight to (dw, db) instead, which is
     faster but sums them in its own order (last-bit differences)."""
 

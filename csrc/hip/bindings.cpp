@@ -96,6 +96,12 @@ std::tuple<torch::Tensor, torch::Tensor> pool_relu_bwd_colsum(
 std::tuple<torch::Tensor, torch::Tensor> thin_conv_pool_wgrad(
     torch::Tensor x, torch::Tensor y_pooled, torch::Tensor idx,
     torch::Tensor dy_pooled, long stride, long pad);
+std::tuple<torch::Tensor, torch::Tensor> thin_conv_pool_wgrad_fused(
+    torch::Tensor x, torch::Tensor y_pooled, torch::Tensor idx,
+    torch::Tensor dy_pooled, long stride, long pad);
+std::string thin_pool_wgrad_impl(std::vector<long> x_shape,
+                                 std::vector<long> w_shape, long stride,
+                                 long pad, bool want_dx);
 std::string conv2d_relu_pool_bwd_route(std::vector<long> x_shape,
                                        std::vector<long> w_shape,
                                        long stride, long pad, bool want_dx,
@@ -220,6 +226,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "direct first-layer (dw, db) from the pooled tensors",
         py::arg("x"), py::arg("y_pooled"), py::arg("idx"),
         py::arg("dy_pooled"), py::arg("stride"), py::arg("pad"));
+  m.def("thin_conv_pool_wgrad_fused", &bflc::thin_conv_pool_wgrad_fused,
+        "first-layer (dw, db) from the pooled tensors, bitwise the "
+        "materialised unpool -> im2col -> split-K GEMM chain",
+        py::arg("x"), py::arg("y_pooled"), py::arg("idx"),
+        py::arg("dy_pooled"), py::arg("stride"), py::arg("pad"));
+  m.def("thin_pool_wgrad_impl", &bflc::thin_pool_wgrad_impl,
+        "what the unpool route runs for the thin first layer: "
+        "fused_mfma | materialized",
+        py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
+        py::arg("pad"), py::arg("want_dx"));
   m.def("conv2d_relu_pool_bwd_route", &bflc::conv2d_relu_pool_bwd_route,
         "route conv2d_relu_pool_bwd takes: thin_direct | unpool",
         py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),

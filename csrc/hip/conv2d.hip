@@ -37,6 +37,7 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
+typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 // col[m][(r*S+s)*C + c8..] = x[n][ih][iw][c8..]  — one 16-B granule per
 // thread iteration; C % 8 == 0.
@@ -390,6 +391,11 @@ __global__ void maxpool_nhwc_bwd(const bf16* __restrict__ dy,
 // thread adds the same values in the same order (the zeros included) and
 // db is BITWISE what that chain gives, as is the plane (0.f + dy is the
 // pool backward's own accumulate, so even the zero signs agree).
+// STORE = false is the bias-gradient-only pass of the fused thin-layer
+// wgrad route: the same rows, per-lane walk and tree with the plane
+// store left out, so db keeps its bits while nothing full-resolution is
+// written.
+template <bool STORE>
 __global__ void pool_relu_bwd_colsum_part_kernel(
     const bf16* __restrict__ yp, const uint8_t* __restrict__ idx,
     const bf16* __restrict__ dyp, bf16* __restrict__ dx, long M, long N,
@@ -402,7 +408,50 @@ __global__ void pool_relu_bwd_colsum_part_kernel(
   const int PH = H >> 1, PW = W >> 1;
   const bf16 zero = f2b(0.f);
   float sj[8] = {};
-  if (c8 < N)
+  if (!STORE && c8 < N) {
+    // The same per-lane ascending walk, so the same sums; what differs
+    // is only how the rows are fetched. The geometry gives this kernel
+    // about one wave per SIMD and ~50 rows per lane, so a load -> add
+    // loop is pure latency (the plane store is not what the storing
+    // variant waits for either): fetch U rows at once, then add them in
+    // order, with no branch between that could pull the loads back to
+    // their uses. Indices are 32-bit (the caller checks M * N < 2^31).
+    constexpr int U = 8;
+    const unsigned Wu = (unsigned)W, Hu = (unsigned)H;
+    for (long m0 = r0 + rl; m0 < r1; m0 += (long)U * RL) {
+      bf16x8_t yv[U], dv[U];
+      u8x8_t iv[U];
+      int code[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long mu = m0 + (long)u * RL;
+        const unsigned m = (unsigned)(mu < r1 ? mu : m0);
+        const unsigned row = m / Wu, n = row / Hu;
+        const unsigned iw = m - row * Wu, ih = row - n * Hu;
+        // past the chunk: a code no window has, so the row adds +0,
+        // which leaves a sum that is never -0 (no addend is) unchanged
+        code[u] = mu < r1 ? (int)((ih & 1) * 2 + (iw & 1)) : 8;
+        const unsigned pm =
+            ((n * PH + (ih >> 1)) * PW + (iw >> 1)) * (unsigned)N +
+            (unsigned)c8;
+        yv[u] = *reinterpret_cast<const bf16x8_t*>(&yp[pm]);
+        dv[u] = *reinterpret_cast<const bf16x8_t*>(&dyp[pm]);
+        iv[u] = *reinterpret_cast<const u8x8_t*>(&idx[pm]);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float a = 0.f;
+          if ((int)iv[u][j] == code[u]) a += b2f(dv[u][j]);
+          bf16 g = f2b(a);
+          if (!(b2f(yv[u][j]) > 0.f)) g = zero;
+          sj[j] += b2f(g);
+        }
+      }
+    }
+  }
+  if (STORE && c8 < N)
     for (long m = r0 + rl; m < r1; m += RL) {  // m = (n, ih, iw)
       const int iw = (int)(m % W), ih = (int)((m / W) % H);
       const long n = m / ((long)W * H);
@@ -556,6 +605,250 @@ __global__ __launch_bounds__(256) void thin_conv_pool_wgrad_final_kernel(
     const int k = o / kWgradAcc, a = o % kWgradAcc;
     if (a < 9) dw[k * 9 + a] = f2b(rs[wv][0]);
     else db[k] = f2b(rs[wv][0]);
+  }
+}
+
+// ---- order-preserving fused wgrad of the thin pooled first layer ----
+// The materialised chain computes dWp[Kout, 16] = dyfull^T @ col with
+// gemm_kernel<32,32,2,1,true,false>: per K slice and per 16-row
+// fragment of Kout one chain of mfma_f32_16x16x32_bf16 over 32 pixels a
+// step, then the fixed-order split-K reduce. dW's bits are fixed by the
+// operand values of each MFMA, their order within a slice and the
+// reduce — not by where the operands came from. This kernel issues the
+// same chain per (slice, fragment) with operands built in registers:
+//   A[kout][k]: the masked unpooled gradient at full-resolution pixel k,
+//     by the expression pool_relu_bwd_colsum_part_kernel stores;
+//   B[k][t]:    x at tap t of pixel k (im2col's row), +0 out of range
+//     and for t >= 9; both +0 past the slice end.
+// so neither the full-resolution plane nor the col matrix exists.
+// One block per slice. A chain is serial, but building its operands is
+// not, and that (VALU issue and 2-byte gathers) is the whole cost: Q
+// waves per fragment each build the operands of CH consecutive k-steps
+// into registers at once, then take turns, in step order, issuing their
+// MFMAs on the one accumulator, which passes through LDS (an exact
+// copy) with a barrier per turn — Q barriers per Q * CH steps, none per
+// step. The build is branch-free:
+//   - the slice's x rows are staged once into LDS as a ZERO-PADDED image
+//     (rows oh + r of H + 2 pad, columns ow + s of OW + 2), so a tap is
+//     an unconditional read at a lane-constant offset from its pixel;
+//   - a table of the slice's pixel PAIRS (OW is even, so two adjacent
+//     pixels share a pooled pixel) is decoded once into LDS: pooled
+//     pixel index, LDS offset of the pair in the padded image, row
+//     parity. Entries past the slice end point at a zero cell and carry
+//     an argmax code no window has, so the tail needs no test;
+//   - the pooled tensors are gathered straight into the A-fragment
+//     layout (lane = channel, 8 consecutive pixels = 4 pairs), the loads
+//     of the next PF steps already in flight.
+
+// Rows [P0, P0 + rows) of the padded image stack (image n, padded row
+// pr <-> n * (OH + 2) + pr) that pixels [k_begin, k_end) read. Host (LDS
+// sizing) and device share it.
+BFLC_HD inline void thin_wgrad_window(const ConvShape& sh, long k_begin,
+                                      long k_end, int* P0, int* rows) {
+  const long ohw = (long)sh.OH * sh.OW;
+  const long n0 = k_begin / ohw, n1 = (k_end - 1) / ohw;
+  const long oh0 = (k_begin - n0 * ohw) / sh.OW;
+  const long oh1 = (k_end - 1 - n1 * ohw) / sh.OW;
+  *P0 = (int)(n0 * (sh.OH + 2) + oh0);
+  *rows = (int)(n1 * (sh.OH + 2) + oh1 + 2) - *P0 + 1;
+}
+
+constexpr int kThinFusedPF = 2;  // k-steps of pooled loads in flight
+constexpr int kThinFusedCH = 6;  // k-steps a wave builds per round
+constexpr long kThinFusedMaxLds = 60 * 1024;  // dynamic; + 4 KB static <= 64 KB
+
+struct PooledRaw {
+  unsigned short dy[4], y[4];
+  uint8_t id[4];
+  int code[4];       // argmax code of the pair's even pixel
+  unsigned xpair[4];  // the pair's two x values at this lane's tap
+};
+
+constexpr int kNoCode = 8;  // matches no argmax code (0..3), +1 included
+
+template <int Q>
+__global__ __launch_bounds__(512) void thin_pool_wgrad_mfma_kernel(
+    const unsigned short* __restrict__ X,
+    const unsigned short* __restrict__ yp, const uint8_t* __restrict__ idx,
+    const unsigned short* __restrict__ dyp, ConvShape sh, long Mpix,
+    long kslice, int cshift, int tbl_pairs, float* __restrict__ part,
+    bf16* __restrict__ dw) {
+  // [tbl_pairs] int2 pair table, then the padded x rows
+  extern __shared__ __align__(16) int lds[];
+  int2* tbl = reinterpret_cast<int2*>(lds);
+  unsigned short* xs = reinterpret_cast<unsigned short*>(lds + 2 * tbl_pairs);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  // wave-uniform by construction; say so, so that the turns below are
+  // scalar branches and no MFMA ever sits under an EXEC mask
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int frag = wave / Q, wq = wave % Q;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const int OH = sh.OH, PW = sh.OW >> 1, PH = sh.OH >> 1;
+  const int WP = sh.OW + 2, OHP = sh.OH + 2;
+  const int Kout = sh.Kout;
+  const long k_begin = (long)blockIdx.x * kslice;
+  const long k_end = min(Mpix, k_begin + kslice);
+  const int npairs = (int)((k_end - k_begin) >> 1);  // both are even
+  const int nsteps = (int)((k_end - k_begin + 31) >> 5);
+
+  int P0, rows;
+  thin_wgrad_window(sh, k_begin, k_end, &P0, &rows);
+  // zero cells after the window: an invalid pair points here, and every
+  // tap offset (< 2 * WP + 4) from it still reads +0
+  const int zcell = rows * WP;
+
+  // ---- pair table ----
+  {
+    const unsigned q0 = (unsigned)(k_begin >> 1);
+    for (int i = tid; i < tbl_pairs; i += (int)blockDim.x) {
+      int2 e = {0, zcell | (kNoCode << 16)};
+      if (i < npairs) {
+        const unsigned q = q0 + i;
+        const unsigned row = q / (unsigned)PW;
+        const unsigned n = row / (unsigned)OH;
+        const int pw = (int)(q - row * PW), oh = (int)(row - n * OH);
+        e.x = ((int)n * PH + (oh >> 1)) * PW + pw;
+        e.y = (((int)n * OHP + oh - P0) * WP + 2 * pw) |
+              (((oh & 1) * 2) << 16);
+      }
+      tbl[i] = e;
+    }
+  }
+  // ---- stage the slice's padded x rows: CW columns x RPP rows a pass,
+  // four passes of loads in flight ----
+  {
+    const int CW = 1 << cshift;  // <= 64 <= blockDim.x
+    const int RPP = (int)blockDim.x >> cshift;
+    const int col = tid & (CW - 1);
+    int j = tid >> cshift;
+    int n = (P0 + j) / OHP, pr = (P0 + j) - n * OHP;
+    const int rwraps = (RPP + OHP - 1) / OHP;
+    while (j < rows) {
+      unsigned short v[4];
+      int dst[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int ih = pr - sh.pad;
+        const bool rok = j < rows && ih >= 0 && ih < sh.H;
+        dst[u] = j < rows ? j * WP : -1;
+        const int iw = col - sh.pad;
+        const bool ok = rok && col < WP && iw >= 0 && iw < sh.W;
+        const unsigned short raw = X[ok ? (n * sh.H + ih) * sh.W + iw : 0];
+        v[u] = ok ? raw : (unsigned short)0;
+        // columns beyond CW (OW > 62) are walked here, one at a time
+        for (int c = col + CW; c < WP; c += CW) {
+          const int iwc = c - sh.pad;
+          const bool okc = rok && iwc >= 0 && iwc < sh.W;
+          const unsigned short rc =
+              X[okc ? (n * sh.H + ih) * sh.W + iwc : 0];
+          if (dst[u] >= 0) xs[dst[u] + c] = okc ? rc : (unsigned short)0;
+        }
+        j += RPP;
+        pr += RPP;
+        for (int t = 0; t < rwraps; ++t) {
+          const bool w = pr >= OHP;
+          pr -= w ? OHP : 0;
+          n += w ? 1 : 0;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (dst[u] >= 0 && col < WP) xs[dst[u] + col] = v[u];
+    }
+    for (int z = tid; z < 2 * WP + 4; z += (int)blockDim.x) xs[zcell + z] = 0;
+  }
+  __syncthreads();
+
+  const int ch = frag * 16 + l15;  // A row: output channel
+  const int chc = ch < Kout ? ch : 0;
+  const int cadd = ch < Kout ? 0 : kNoCode;   // rows >= Kout stay +0
+  const int tr = l15 / 3, ts = l15 - tr * 3;  // B column: tap (r, s)
+  const bool tap_ok = l15 < 9;                // columns >= 9 stay +0
+  const int tbase = tr * WP + ts;
+
+  // this lane's four pairs of k-step `st`; steps past the slice read
+  // the all-invalid table row after it
+  auto load_step = [&](PooledRaw& raw, int st) {
+    st = min(st, nsteps);
+    const int4* t = reinterpret_cast<const int4*>(&tbl[st * 16 + l4 * 4]);
+    const int4 e01 = t[0], e23 = t[1];
+    const int po[4] = {e01.x, e01.z, e23.x, e23.z};
+    const int xc[4] = {e01.y, e01.w, e23.y, e23.w};
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const unsigned o = (unsigned)(po[jj] * Kout + chc);
+      raw.dy[jj] = dyp[o];
+      raw.y[jj] = yp[o];
+      raw.id[jj] = idx[o];
+      raw.code[jj] = (xc[jj] >> 16) + cadd;
+      const int xa = tap_ok ? (xc[jj] & 0xffff) + tbase : zcell;
+      raw.xpair[jj] = (unsigned)xs[xa] | ((unsigned)xs[xa + 1] << 16);
+    }
+  };
+
+  constexpr int PF = kThinFusedPF, CH = kThinFusedCH;
+  __shared__ f32x4_t accs[4][64];  // the accumulator between turns
+  const bf16 zero = f2b(0.f);
+  f32x4_t acc = {};
+  for (int base = 0; base < nsteps; base += Q * CH) {
+    const int my0 = base + wq * CH;
+    // ---- build this wave's CH steps ----
+    u16x8_t av[CH], bv[CH];
+    PooledRaw raw[PF];
+#pragma unroll
+    for (int i = 0; i < PF; ++i) load_step(raw[i], my0 + i);
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const PooledRaw& rw = raw[i % PF];
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const float dyf = __uint_as_float((unsigned)rw.dy[jj] << 16);
+        const float yf = __uint_as_float((unsigned)rw.y[jj] << 16);
+        bv[i][jj * 2] = (unsigned short)(rw.xpair[jj] & 0xffff);
+        bv[i][jj * 2 + 1] = (unsigned short)(rw.xpair[jj] >> 16);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const int code = rw.code[jj] + p;
+          float a = 0.f;
+          if ((int)rw.id[jj] == code) a += dyf;
+          bf16 gv = f2b(a);
+          if (!(yf > 0.f)) gv = zero;
+          av[i][jj * 2 + p] = __builtin_bit_cast(unsigned short, gv);
+        }
+      }
+      if (i + PF < CH) load_step(raw[i % PF], my0 + i + PF);
+    }
+    // ---- the chain, in step order: one turn per wave ----
+#pragma unroll
+    for (int t = 0; t < Q; ++t) {
+      if (wq == t && my0 < nsteps) {  // wave-uniform
+        if (my0 > 0) acc = accs[frag][lane];
+#pragma unroll
+        for (int i = 0; i < CH; ++i)
+          if (my0 + i < nsteps)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                __builtin_bit_cast(bf16x8_t, av[i]),
+                __builtin_bit_cast(bf16x8_t, bv[i]), acc, 0, 0, 0);
+        accs[frag][lane] = acc;
+      }
+      __syncthreads();
+    }
+  }
+  if (wq != 0) return;
+  acc = accs[frag][lane];  // the last turn's, whichever wave took it
+
+  // D: lane holds rows l4 * 4 + r of the fragment, column l15 (= tap)
+  if (l15 < 9) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = frag * 16 + l4 * 4 + r;
+      if (row >= Kout) continue;
+      if (part)
+        part[((long)blockIdx.x * Kout + row) * 9 + l15] = acc[r];
+      else  // single slice: the GEMM epilogue's store with a null bias
+        dw[row * 9 + l15] = f2b(acc[r] + 0.f);
+    }
   }
 }
 
@@ -978,6 +1271,56 @@ void check_pooled(const torch::Tensor& y, const torch::Tensor& idx,
               "pooled backward: y, idx, dy must share one NHWC shape");
 }
 
+// BFLC_THIN_FUSED_WGRAD: 1 (default) routes the thin first layer's
+// default backward through the order-preserving fused kernel, 0 keeps
+// the materialised chain (A/B runs; the results are bitwise the same).
+bool thin_fused_wgrad_gate() {
+  static const bool v = env_gate("BFLC_THIN_FUSED_WGRAD", 1) != 0;
+  return v;
+}
+
+// The slices of the materialised chain's GEMM, dWp[Kout, 16] over K =
+// Mpix, and whether the fused kernel can stand in for it: the plan must
+// be the small-tile kernel's (whose chain the fused kernel issues) and
+// every slice's pair table and padded x rows must fit the LDS budget.
+struct ThinFusedPlan {
+  bool ok = false;
+  long S = 1, kslice = 0;
+  int tbl_pairs = 0;  // pair-table entries: a slice + one all-invalid step
+  long lds = 0;       // LDS bytes: table + tallest window + zero cells
+  int cshift = 0;     // staging columns per pass = 1 << cshift (<= 64)
+};
+
+ThinFusedPlan thin_fused_plan(const ConvShape& sh) {
+  ThinFusedPlan t;
+  if (!thin_wgrad_eligible(sh) || sh.N <= 0) return t;
+  const long Mpix = sh.M();
+  const long kp = (sh.RSC() + 7) / 8 * 8;
+  const GemmPlan p = gemm_dense_plan(sh.Kout, kp, Mpix, true, false);
+  // the kernel indexes x, the pooled tensors and its rows in 32 bits
+  const long lim = 1L << 31;
+  if (p.path != GemmPath::kSmall || kp != 16 || Mpix * sh.Kout >= lim ||
+      (long)sh.N * sh.H * sh.W >= lim || (long)sh.N * (sh.OH + 2) >= lim)
+    return t;
+  t.S = p.S;
+  t.kslice = p.kslice;
+  int rows_max = 0;
+  for (long s = 0; s < p.S; ++s) {
+    int P0, rows;
+    thin_wgrad_window(sh, s * p.kslice,
+                      std::min(Mpix, (s + 1) * p.kslice), &P0, &rows);
+    rows_max = std::max(rows_max, rows);
+  }
+  const long xelems = (long)(rows_max + 2) * (sh.OW + 2) + 4;
+  const long pairs = (p.kslice / 32 + 1) * 16;  // + one all-invalid step
+  t.tbl_pairs = (int)pairs;
+  t.lds = pairs * 8 + (xelems + 1) / 2 * 4;
+  while (t.cshift < 6 && (1 << t.cshift) < sh.OW + 2) ++t.cshift;
+  // the x offset shares a table word with the row parity (16 bits)
+  t.ok = t.lds <= kThinFusedMaxLds && xelems <= 32768;
+  return t;
+}
+
 }  // namespace
 
 torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
@@ -1015,7 +1358,7 @@ std::tuple<torch::Tensor, torch::Tensor> pool_relu_bwd_colsum(
   auto part = torch::empty({g.chunks, N},
                            dy_pooled.options().dtype(at::kFloat));
   if (M > 0) {
-    hipLaunchKernelGGL(pool_relu_bwd_colsum_part_kernel,
+    hipLaunchKernelGGL(pool_relu_bwd_colsum_part_kernel<true>,
                        dim3(g.cblocks, g.chunks), dim3(256), 0, cur_stream(),
                        (const bf16*)y_pooled.data_ptr(),
                        idx.data_ptr<uint8_t>(),
@@ -1070,6 +1413,82 @@ std::tuple<torch::Tensor, torch::Tensor> thin_conv_pool_wgrad(
   return {dw, db};
 }
 
+// (dw, db) of the thin first layer, BITWISE the materialised chain
+// pool_relu_bwd_colsum -> conv2d_bwd (im2col, split-K GEMM, reduce,
+// narrow copy): dW from the same MFMA chains and the same reduce, db
+// from the unpool kernel's own walk with the plane store left out.
+std::tuple<torch::Tensor, torch::Tensor> thin_conv_pool_wgrad_fused(
+    torch::Tensor x, torch::Tensor y_pooled, torch::Tensor idx,
+    torch::Tensor dy_pooled, long stride, long pad) {
+  CHECK_GPU(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 4,
+              "thin_conv_pool_wgrad_fused: bf16 NHWC x");
+  check_pooled(y_pooled, idx, dy_pooled);
+  const auto sh = make_shape_dims(
+      x.sizes().vec(), {y_pooled.size(3), 3, 3, x.size(3)}, stride, pad);
+  const ThinFusedPlan t = thin_fused_plan(sh);
+  TORCH_CHECK(t.ok,
+              "thin_conv_pool_wgrad_fused: 3x3, C == 1, stride 1, even "
+              "OH/OW, Kout % 8 == 0 and Kout <= 64, on the small-tile "
+              "split-K plan, only");
+  TORCH_CHECK(y_pooled.size(0) == sh.N && y_pooled.size(1) == sh.OH / 2 &&
+              y_pooled.size(2) == sh.OW / 2,
+              "thin_conv_pool_wgrad_fused: pooled shape does not match x");
+  const long Mpix = sh.M();
+  const int N = sh.Kout;
+  auto dw = torch::empty({(long)N, 3, 3, 1}, x.options());
+  auto db = torch::empty({(long)N}, x.options());
+
+  torch::Tensor part;
+  if (t.S > 1)
+    part = torch::empty({t.S, (long)N, 9}, x.options().dtype(at::kFloat));
+  const int frags = (N + 15) / 16;
+  // waves per fragment: 4, or 2 where four fragments fill the block
+  auto* kern = frags <= 2 ? thin_pool_wgrad_mfma_kernel<4>
+                          : thin_pool_wgrad_mfma_kernel<2>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)t.S),
+                     dim3(frags * (frags <= 2 ? 4 : 2) * 64), (size_t)t.lds,
+                     cur_stream(), (const unsigned short*)x.data_ptr(),
+                     (const unsigned short*)y_pooled.data_ptr(),
+                     idx.data_ptr<uint8_t>(),
+                     (const unsigned short*)dy_pooled.data_ptr(), sh, Mpix,
+                     t.kslice, t.cshift, t.tbl_pairs,
+                     t.S > 1 ? part.data_ptr<float>() : nullptr,
+                     (bf16*)dw.data_ptr());
+  HIP_CHECK(hipGetLastError());
+  if (t.S > 1) {
+    auto dw2 = dw.view({(long)N, 9});
+    splitk_reduce_plain(part, dw2);
+  }
+
+  const ColsumGeom g = colsum_geom(Mpix, N);  // pool_relu_bwd_colsum's
+  auto cpart = torch::empty({g.chunks, (long)N},
+                            x.options().dtype(at::kFloat));
+  hipLaunchKernelGGL(pool_relu_bwd_colsum_part_kernel<false>,
+                     dim3(g.cblocks, g.chunks), dim3(256), 0, cur_stream(),
+                     (const bf16*)y_pooled.data_ptr(),
+                     idx.data_ptr<uint8_t>(),
+                     (const bf16*)dy_pooled.data_ptr(), (bf16*)nullptr, Mpix,
+                     (long)N, sh.OH, sh.OW, g.G, g.rows,
+                     cpart.data_ptr<float>());
+  HIP_CHECK(hipGetLastError());
+  colsum_finalize(cpart, db);
+  return {dw, db};
+}
+
+// Which implementation conv2d_relu_pool_bwd's "unpool" route runs for
+// the thin first layer: "fused_mfma" (thin_conv_pool_wgrad_fused) or
+// "materialized" (unpool plane -> im2col -> GEMM). Both give the same
+// bits; the query lets a test know which one it exercised.
+std::string thin_pool_wgrad_impl(std::vector<long> x_shape,
+                                 std::vector<long> w_shape, long stride,
+                                 long pad, bool want_dx) {
+  const auto sh = make_shape_dims(x_shape, w_shape, stride, pad);
+  return !want_dx && thin_fused_wgrad_gate() && thin_fused_plan(sh).ok
+             ? "fused_mfma"
+             : "materialized";
+}
+
 // Route conv2d_relu_pool_bwd takes, so a test cannot pass through the
 // wrong path: "thin_direct" (allowed, no dx wanted, thin geometry) or
 // "unpool". The unpool route is bitwise the two-op backward; the direct
@@ -1101,6 +1520,13 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_relu_pool_bwd(
   if (allow_direct && !want_dx && thin_wgrad_eligible(sh)) {
     auto [dw, db] = thin_conv_pool_wgrad(x, y_pooled, idx, dy_pooled,
                                          stride, pad);
+    return {none, dw.view(w.sizes()), want_db ? db : none};
+  }
+  // the unpool route of the thin first layer without its plane, col
+  // matrix and narrow copy: same bits (thin_conv_pool_wgrad_fused)
+  if (!want_dx && thin_fused_wgrad_gate() && thin_fused_plan(sh).ok) {
+    auto [dw, db] = thin_conv_pool_wgrad_fused(x, y_pooled, idx, dy_pooled,
+                                               stride, pad);
     return {none, dw.view(w.sizes()), want_db ? db : none};
   }
   auto [dyf, db] = pool_relu_bwd_colsum(

@@ -54,6 +54,11 @@ inline PlanRow plan_row(const GemmPlan& p) {
 }
 // The plan gemm_bf16_raw takes for a plain-store call without bn_stats.
 PlanRow gemm_plan_route(long M, long N, long K, bool ta, bool tb);
+// That plan itself, and the plain-store split-K reduce that call ends
+// with (part [S, M, N] fp32 -> out [M, N] bf16): for a kernel that feeds
+// the same MFMA chains per slice without going through gemm_bf16_raw.
+GemmPlan gemm_dense_plan(long M, long N, long K, bool ta, bool tb);
+void splitk_reduce_plain(const torch::Tensor& part, torch::Tensor& out);
 
 // The implicit-GEMM conv entries below and the plan each launches
 // (path "none": the entry returns false for this shape). Pure host

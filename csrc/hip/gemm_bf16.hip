@@ -2126,6 +2126,21 @@ PlanRow gemm_plan_route(long M, long N, long K, bool ta, bool tb) {
                              wgrad_small_gate()));
 }
 
+// The same plan, for a kernel outside this file that has to reproduce a
+// dense launch's split-K slices (the fused thin-layer wgrad, conv2d.hip).
+GemmPlan gemm_dense_plan(long M, long N, long K, bool ta, bool tb) {
+  return plan_dense(M, N, K, ta, tb, true, false, wgrad_small_gate());
+}
+
+// The plain-store split-K reduce gemm_bf16_raw ends with, over partials
+// produced outside this file: out[M, N] = bf16(sum over S of part[s]),
+// same kernel choice and fixed order for a given (S, M * N, N % 4).
+void splitk_reduce_plain(const torch::Tensor& part, torch::Tensor& out) {
+  launch_splitk_reduce(part.data_ptr<float>(), part.size(0), part.size(1),
+                       part.size(2), (bf16*)out.data_ptr(), nullptr, 0,
+                       EpStore::kPlain, 0);
+}
+
 std::tuple<long, long, long, long> colsum_geom_query(long M, long N) {
   const ColsumGeom g = colsum_geom(M, N);
   return {g.G, g.cblocks, g.rows, g.chunks};
