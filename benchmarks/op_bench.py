@@ -137,6 +137,18 @@ def main():
         out[f"score.{name}.fused"] = timeit(
             lambda: h_ops.conv2d_relu_pool_fwd(x, w, b, stride, pad),
             args.iters)
+        # what the gemm256_pool route launches (BFLC_HALO_CONV), next to
+        # both of its implementations pinned
+        impl = h_ops.conv_fwd_pool_impl(list(x.shape), list(w.shape), stride,
+                                        pad)
+        out[f"score.{name}.fused_impl"] = impl
+        if impl == "halo_mfma":
+            out[f"score.{name}.fused_gemm256"] = timeit(
+                lambda: h_ops.conv2d_relu_pool_fwd(x, w, b, stride, pad, 0,
+                                                   "gemm256"), args.iters)
+            out[f"score.{name}.fused_halo_mfma"] = timeit(
+                lambda: h_ops.conv2d_relu_pool_fwd(x, w, b, stride, pad, 0,
+                                                   "halo_mfma"), args.iters)
 
     # training conv + ReLU + 2x2 pool stages: the two-op forward (conv
     # writes the full plane, pool reads it back) vs the fused one that
@@ -162,6 +174,18 @@ def main():
         out[f"train.{name}.fwd_fused_idx"] = timeit(
             lambda: h_ops.conv2d_relu_pool_fwd_idx(x, w, b, stride, pad),
             args.iters)
+        impl = h_ops.conv_fwd_pool_impl(list(x.shape), list(w.shape), stride,
+                                        pad)
+        out[f"train.{name}.fwd_fused_impl"] = impl
+        if impl == "halo_mfma":
+            out[f"train.{name}.fwd_fused_idx_gemm256"] = timeit(
+                lambda: h_ops.conv2d_relu_pool_fwd_idx(x, w, b, stride, pad,
+                                                       0, "gemm256"),
+                args.iters)
+            out[f"train.{name}.fwd_fused_idx_halo_mfma"] = timeit(
+                lambda: h_ops.conv2d_relu_pool_fwd_idx(x, w, b, stride, pad,
+                                                       0, "halo_mfma"),
+                args.iters)
         yfull = h_ops.conv2d_fwd(x, w, b, stride, pad, True)
         yp, idx = h_ops.maxpool2d_fwd(yfull, 2, 2, True)
         dy = torch.randn_like(yp)

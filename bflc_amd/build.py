@@ -77,6 +77,7 @@ HIP_SOURCES = [
     "elementwise.hip",
     "softmax_ce.hip",
     "gemm_bf16.hip",
+    "halo_conv.hip",
     "conv2d.hip",
     "batchnorm.hip",
     "reduce.hip",

@@ -81,7 +81,14 @@ torch::Tensor maxpool2d_bwd(torch::Tensor dy, torch::Tensor idx,
                             std::vector<long> in_shape, long kernel,
                             long stride);
 torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
-                                   torch::Tensor b, long stride, long pad);
+                                   torch::Tensor b, long stride, long pad,
+                                   long max_blocks, std::string impl);
+std::string conv_fwd_pool_impl(std::vector<long> x_shape,
+                               std::vector<long> w_shape, long stride,
+                               long pad);
+long halo_conv_group_images_query(std::vector<long> x_shape,
+                                  std::vector<long> w_shape, long stride,
+                                  long pad);
 std::string conv2d_relu_pool_route(std::vector<long> x_shape,
                                    std::vector<long> w_shape, long stride,
                                    long pad);
@@ -89,7 +96,7 @@ PlanRow conv_plan_route(const std::string& entry, std::vector<long> x_shape,
                         std::vector<long> w_shape, long stride, long pad);
 std::tuple<torch::Tensor, torch::Tensor> conv2d_relu_pool_fwd_idx(
     torch::Tensor x, torch::Tensor w, torch::Tensor b, long stride,
-    long pad);
+    long pad, long max_blocks, std::string impl);
 std::tuple<torch::Tensor, torch::Tensor> pool_relu_bwd_colsum(
     torch::Tensor y_pooled, torch::Tensor idx, torch::Tensor dy_pooled,
     std::vector<long> out_shape);
@@ -205,8 +212,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool2d_bwd", &bflc::maxpool2d_bwd);
   m.def("conv2d_relu_pool_fwd", &bflc::conv2d_relu_pool_fwd,
         "grad-free conv + bias + ReLU + 2x2/2 maxpool, pooled in the conv "
-        "epilogue where a fused route applies: [N, OH/2, OW/2, Kout]",
+        "epilogue where a fused route applies: [N, OH/2, OW/2, Kout]. "
+        "max_blocks > 0 caps the halo kernel's grid; impl pins gemm256 | "
+        "halo_mfma ('' = conv_fwd_pool_impl's answer)",
         py::arg("x"), py::arg("w"), py::arg("b"), py::arg("stride"),
+        py::arg("pad"), py::arg("max_blocks") = 0, py::arg("impl") = "");
+  m.def("conv_fwd_pool_impl", &bflc::conv_fwd_pool_impl,
+        "what the gemm256_pool route launches: halo_mfma | gemm256",
+        py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
+        py::arg("pad"));
+  m.def("halo_conv_group_images", &bflc::halo_conv_group_images_query,
+        "images per LDS group of the halo kernel (0: not its geometry)",
+        py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
         py::arg("pad"));
   m.def("conv2d_relu_pool_route", &bflc::conv2d_relu_pool_route,
         "route conv2d_relu_pool_fwd takes: gemm256_pool | thin_pool | "
@@ -215,9 +232,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pad"));
   m.def("conv2d_relu_pool_fwd_idx", &bflc::conv2d_relu_pool_fwd_idx,
         "training conv + bias + ReLU + 2x2/2 maxpool: (y_pooled, idx), "
-        "same routes as conv2d_relu_pool_fwd",
+        "same routes and options as conv2d_relu_pool_fwd",
         py::arg("x"), py::arg("w"), py::arg("b"), py::arg("stride"),
-        py::arg("pad"));
+        py::arg("pad"), py::arg("max_blocks") = 0, py::arg("impl") = "");
   m.def("pool_relu_bwd_colsum", &bflc::pool_relu_bwd_colsum,
         "unpool + ReLU mask + bias grad in one pass: (dy_full_masked, db)",
         py::arg("y_pooled"), py::arg("idx"), py::arg("dy_pooled"),

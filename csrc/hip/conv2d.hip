@@ -1222,11 +1222,22 @@ namespace {
 // want_idx = false and runs exactly the kernels it ran before.
 std::tuple<torch::Tensor, torch::Tensor> relu_pool_fwd_impl(
     const torch::Tensor& x, const torch::Tensor& w, const torch::Tensor& b,
-    long stride, long pad, bool want_idx) {
+    long stride, long pad, bool want_idx, long max_blocks = 0,
+    const std::string& impl = "") {
   CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(w);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "conv: bf16 only");
   auto sh = make_shape(x, w, stride, pad);
-  const PoolRoute route = pool_route(sh);
+  // impl: "" = what conv_fwd_pool_impl reports; "gemm256" / "halo_mfma"
+  // pin one side of the conv2 pooled forward (tests, op benchmark)
+  TORCH_CHECK(impl.empty() || impl == "gemm256" || impl == "halo_mfma",
+              "conv2d_relu_pool: impl is '' | gemm256 | halo_mfma");
+  const HaloMode halo = impl.empty()        ? HaloMode::kAuto
+                        : impl == "gemm256" ? HaloMode::kOff
+                                            : HaloMode::kForce;
+  TORCH_CHECK(halo != HaloMode::kForce || halo_conv_geometry_ok(sh),
+              "conv2d_relu_pool: shape outside the halo kernel's geometry");
+  const PoolRoute route =
+      halo == HaloMode::kForce ? PoolRoute::kGemm256 : pool_route(sh);
   if (route != PoolRoute::kUnfused) {
     auto w2 = w.view({(long)sh.Kout, sh.RSC()});
     auto bc = b.contiguous();
@@ -1238,7 +1249,8 @@ std::tuple<torch::Tensor, torch::Tensor> relu_pool_fwd_impl(
     uint8_t* ip = want_idx ? idx.data_ptr<uint8_t>() : nullptr;
     const bool done =
         route == PoolRoute::kGemm256
-            ? gemm_conv_fwd_pool_raw(x, w2, y, sh, &bc, true, ip)
+            ? gemm_conv_fwd_pool_raw(x, w2, y, sh, &bc, true, ip, halo,
+                                     (int)max_blocks)
             : gemm_thin_conv_pool_raw(
                   x, pad_w2(w2, (sh.RSC() + 7) / 8 * 8), y, sh, &bc, true,
                   ip);
@@ -1324,8 +1336,31 @@ ThinFusedPlan thin_fused_plan(const ConvShape& sh) {
 }  // namespace
 
 torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
-                                   torch::Tensor b, long stride, long pad) {
-  return std::get<0>(relu_pool_fwd_impl(x, w, b, stride, pad, false));
+                                   torch::Tensor b, long stride, long pad,
+                                   long max_blocks, std::string impl) {
+  return std::get<0>(
+      relu_pool_fwd_impl(x, w, b, stride, pad, false, max_blocks, impl));
+}
+
+// What the "gemm256_pool" route launches for these shapes: "halo_mfma"
+// (halo_conv_pool_kernel) or "gemm256" (gemm256_kernel, also the answer
+// for shapes that route does not take at all). Same bits either way.
+std::string conv_fwd_pool_impl(std::vector<long> x_shape,
+                               std::vector<long> w_shape, long stride,
+                               long pad) {
+  const auto sh = make_shape_dims(x_shape, w_shape, stride, pad);
+  return pool_route(sh) == PoolRoute::kGemm256 && halo_conv_gate(sh)
+             ? "halo_mfma"
+             : "gemm256";
+}
+
+// Images per LDS group of the halo kernel for these shapes (0: the
+// geometry is not the kernel's).
+long halo_conv_group_images_query(std::vector<long> x_shape,
+                                  std::vector<long> w_shape, long stride,
+                                  long pad) {
+  return halo_conv_group_images(
+      make_shape_dims(x_shape, w_shape, stride, pad));
 }
 
 // Training forward: the same routes, plus the u8 argmax plane the
@@ -1333,8 +1368,8 @@ torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
 // maxpool2d_fwd(2, 2, want_idx=true).
 std::tuple<torch::Tensor, torch::Tensor> conv2d_relu_pool_fwd_idx(
     torch::Tensor x, torch::Tensor w, torch::Tensor b, long stride,
-    long pad) {
-  return relu_pool_fwd_impl(x, w, b, stride, pad, true);
+    long pad, long max_blocks, std::string impl) {
+  return relu_pool_fwd_impl(x, w, b, stride, pad, true, max_blocks, impl);
 }
 
 // (masked full-resolution dy, db) from the pooled tensors; out_shape is

@@ -91,10 +91,31 @@ bool gemm_conv_fwd_pool_eligible(const ConvShape& sh);
 // idx (optional, [N, OH/2, OW/2, Kout] u8): the training forward also
 // gets the argmax code dy*2 + dx of each window, chosen as
 // maxpool2d_fwd chooses it (strict > from -inf on the rounded values).
+// halo: which kernel a gated shape (halo_conv_gate) runs - kAuto the
+// halo kernel, kOff gemm256_kernel as if the gate were closed, kForce
+// the halo kernel on its geometry alone (halo_conv_geometry_ok; tests
+// and the op benchmark, the bits are the unsplit chain's).
+// max_blocks > 0 caps the halo kernel's grid.
+enum class HaloMode { kAuto, kOff, kForce };
 bool gemm_conv_fwd_pool_raw(const torch::Tensor& x, const torch::Tensor& w2,
                             torch::Tensor& y, const ConvShape& sh,
                             const torch::Tensor* bias, bool relu,
-                            uint8_t* idx = nullptr);
+                            uint8_t* idx = nullptr,
+                            HaloMode halo = HaloMode::kAuto,
+                            int max_blocks = 0);
+
+// Halo-tile pooled conv forward (halo_conv.hip): C == 32, 3x3, stride
+// 1, pad 1, Kout == 64, even OH/OW, whole zero-ringed images in LDS.
+// Bitwise gemm256_kernel's single-slice pooled forward.
+bool halo_conv_geometry_ok(const ConvShape& sh);
+// images a block stages per group for this geometry (0: not eligible)
+int halo_conv_group_images(const ConvShape& sh);
+// geometry && the fwd_pool plan is an unsplit gemm256 && BFLC_HALO_CONV
+bool halo_conv_gate(const ConvShape& sh);
+void halo_conv_fwd_pool_launch(const torch::Tensor& x,
+                               const torch::Tensor& w2, torch::Tensor& y,
+                               const ConvShape& sh, const torch::Tensor* bias,
+                               bool relu, uint8_t* idx, int max_blocks);
 bool gemm_thin_conv_pool_eligible(const ConvShape& sh, long KT);
 bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
                              const torch::Tensor& w2p, torch::Tensor& y,

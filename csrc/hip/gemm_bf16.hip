@@ -2233,12 +2233,22 @@ bool conv_implicit_gemm(const torch::Tensor& x, const torch::Tensor& w2,
                         const torch::Tensor* bias, bool relu,
                         std::pair<torch::Tensor, torch::Tensor>* bn_stats
                         = nullptr, bool pool = false,
-                        uint8_t* pool_idx = nullptr) {
+                        uint8_t* pool_idx = nullptr,
+                        HaloMode halo = HaloMode::kAuto,
+                        int max_blocks = 0) {
   const ConvEntry e = CMODE == 2 ? ConvEntry::kDgrad
                                  : (pool ? ConvEntry::kFwdPool
                                          : ConvEntry::kFwd);
   const GemmPlan p = gemm_conv_plan(e, sh);
   if (p.path == GemmPath::kNone || (pool && bn_stats)) return false;
+  if constexpr (CMODE == 1) {
+    // conv2's pooled forward: whole images in LDS, same MFMA chain
+    if (pool && halo != HaloMode::kOff && halo_conv_gate(sh)) {
+      halo_conv_fwd_pool_launch(x, w2, y, sh, bias, relu, pool_idx,
+                                max_blocks);
+      return true;
+    }
+  }
   const GemmDims d = conv_gemm_dims(e, sh);
   const long M = d.M, N = d.N, K = d.K;
   const bf16* a = (const bf16*)x.data_ptr();
@@ -2318,8 +2328,13 @@ bool gemm_conv_fwd_pool_eligible(const ConvShape& sh) {
 bool gemm_conv_fwd_pool_raw(const torch::Tensor& x, const torch::Tensor& w2,
                             torch::Tensor& y, const ConvShape& sh,
                             const torch::Tensor* bias, bool relu,
-                            uint8_t* idx) {
-  return conv_implicit_gemm<1>(x, w2, y, sh, bias, relu, nullptr, true, idx);
+                            uint8_t* idx, HaloMode halo, int max_blocks) {
+  if (halo == HaloMode::kForce) {
+    halo_conv_fwd_pool_launch(x, w2, y, sh, bias, relu, idx, max_blocks);
+    return true;
+  }
+  return conv_implicit_gemm<1>(x, w2, y, sh, bias, relu, nullptr, true, idx,
+                               halo, max_blocks);
 }
 
 bool gemm_conv_dgrad_raw(const torch::Tensor& dy, const torch::Tensor& wrot2,
