@@ -6,7 +6,8 @@ shapes) with CUDA events and prints one JSON blob — a finer-grained
 regression harness than rocprof kernel stats (which mix call sites):
 run it before and after a kernel change and diff the per-shape numbers.
 
-    python benchmarks/op_bench.py [--iters 50] [--only conv,score,train,gemm]
+    python benchmarks/op_bench.py [--iters 50] \
+        [--only conv,score,train,gemm,norm]
 """
 import argparse
 import json
@@ -77,11 +78,31 @@ GEMMS = [
     ("sq.2048", 2048, 2048, 2048),
 ]
 
+# (name, N, H, C, groups) normalisation inputs: the ResNet-20 stages at
+# batch 512, ResNet-50 layers at batch 64, and two shapes around the
+# GroupNorm slab/split threshold (64 KiB and 128 KiB per sample)
+NORMS = [
+    ("r20.s1", 512, 32, 16, 8),
+    ("r20.s2", 512, 16, 32, 8),
+    ("r20.s3", 512, 8, 64, 8),
+    ("r50.stem", 64, 112, 64, 32),
+    ("r50.c2", 64, 56, 64, 32),
+    ("r50.c2.out", 64, 56, 256, 32),
+    ("r50.c3.out", 64, 28, 512, 32),
+    ("r50.c4.out", 64, 14, 1024, 32),
+    ("r50.c5", 64, 7, 512, 32),
+    ("r50.c5.out", 64, 7, 2048, 32),
+    ("thr.64k", 256, 32, 32, 8),
+    ("thr.128k", 256, 32, 64, 8),
+]
+
+COPY_BW = 6.29e12  # measured device copy bandwidth, bytes/s
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--only", default="conv,score,train,gemm",
+    ap.add_argument("--only", default="conv,score,train,gemm,norm",
                     help="comma-separated sections to run")
     args = ap.parse_args()
     only = set(args.only.split(","))
@@ -240,6 +261,51 @@ def main():
             lambda: h_ops.linear_fwd(x, w, b, False), args.iters)
         out[f"gemm.{name}.bwd"] = timeit(
             lambda: h_ops.linear_bwd(x, w, dy), args.iters)
+
+    # normalisation layers at the ResNet hot shapes: GroupNorm forward /
+    # backward on every legal route (BFLC_GN_ROUTE pins it), next to the
+    # BN kernels at the same shape — the standalone stats + norm pair
+    # and batchnorm_bwd. The thr.* rows sit on either side of the
+    # slab/split threshold (64 KiB per sample).
+    for name, n, h, c, groups in (NORMS if "norm" in only else []):
+        h_ops = O.hip_ops()
+        x = torch.randn(n, h, h, c, device=dev, dtype=torch.bfloat16)
+        dy = torch.randn_like(x)
+        g = torch.rand(c, device=dev, dtype=torch.bfloat16) + 0.5
+        be = torch.randn(c, device=dev, dtype=torch.bfloat16)
+        tensor_bytes = x.numel() * 2
+
+        def bn_pair():
+            mean, invstd = h_ops.bn_stats(x, 1e-5)
+            return h_ops.batchnorm_norm(x, g, be, mean, invstd, True, None)
+
+        yb, mean, invstd = h_ops.batchnorm_fwd(x, g, be, 1e-5, True, None)
+        out[f"norm.{name}.bn.fwd_stats+norm"] = timeit(bn_pair, args.iters)
+        out[f"norm.{name}.bn.bwd"] = timeit(
+            lambda: h_ops.batchnorm_bwd(x, dy, mean, invstd, g, yb),
+            args.iters)
+        saved = os.environ.pop("BFLC_GN_ROUTE", None)
+        out[f"norm.{name}.gn.route"] = h_ops.groupnorm_route(h, h, c, groups)
+        for route in ("slab", "split"):
+            os.environ["BFLC_GN_ROUTE"] = route
+            if h_ops.groupnorm_route(h, h, c, groups) != route:
+                continue  # slab is not legal at this shape
+            yg, gm, gr = h_ops.groupnorm_fwd(x, g, be, groups, 1e-5, True)
+            t_f = timeit(lambda: h_ops.groupnorm_fwd(x, g, be, groups, 1e-5,
+                                                     True), args.iters)
+            t_b = timeit(lambda: h_ops.groupnorm_bwd(x, dy, gm, gr, g,
+                                                     groups, yg), args.iters)
+            out[f"norm.{name}.gn.{route}.fwd"] = t_f
+            out[f"norm.{name}.gn.{route}.bwd"] = t_b
+            # whole-op traffic floor: fwd reads x, writes y (2 tensor
+            # passes); bwd reads x, dy, y and writes dx (4)
+            out[f"norm.{name}.gn.{route}.fwd_frac_copy_bw"] = \
+                2 * tensor_bytes / (t_f * 1e-6) / COPY_BW
+            out[f"norm.{name}.gn.{route}.bwd_frac_copy_bw"] = \
+                4 * tensor_bytes / (t_b * 1e-6) / COPY_BW
+        os.environ.pop("BFLC_GN_ROUTE", None)
+        if saved is not None:
+            os.environ["BFLC_GN_ROUTE"] = saved
 
     print(json.dumps({"unit": "us_per_call", "ops": out}, indent=1))
 

@@ -80,6 +80,7 @@ HIP_SOURCES = [
     "halo_conv.hip",
     "conv2d.hip",
     "batchnorm.hip",
+    "groupnorm.hip",
     "reduce.hip",
     "bindings.cpp",
 ]

@@ -40,6 +40,8 @@ class FLConfig:
     seed: int = 42
     dtype: str = "bf16"            # compute dtype on GPU; fp32 on CPU tests
     optimizer: str = "sgd"         # sgd | adam (reference main.py:126-127)
+    norm_groups: int = 0           # ResNets: 0 = batch-stats BatchNorm,
+                                   # > 0 = GroupNorm with that many groups
 
     # --- sharding ---
     partition: str = "iid"         # iid | dirichlet (non-IID)
@@ -65,6 +67,8 @@ class FLConfig:
         if self.client_num > 1 and \
                 self.needed_update_count > self.client_num - self.comm_count:
             raise ValueError("needed_update_count exceeds trainer count")
+        if self.norm_groups < 0:
+            raise ValueError("norm_groups must be >= 0")
 
     # ------------------------------------------------------------------
     @classmethod

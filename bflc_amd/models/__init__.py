@@ -70,6 +70,11 @@ class FemnistCNN(FlatModel):
 
 def build_model(cfg, device, compute_dtype=None) -> FlatModel:
     name = cfg.model
+    if getattr(cfg, "norm_groups", 0) > 0 and \
+            name in ("logreg", "mlp", "femnist_cnn"):
+        raise ValueError(
+            f"norm_groups={cfg.norm_groups} set for model '{name}', which "
+            "has no normalisation layers; it applies to resnet20/resnet50")
     if name == "logreg":
         m = LogReg(cfg, device, compute_dtype)
     elif name == "mlp":

@@ -1,6 +1,7 @@
 """ResNet-20 (CIFAR, BASELINE config 3) and ResNet-50 (ImageNet-shape,
 BASELINE config 5) built from the gfx950 op set: NHWC MFMA conv (1x1 =
-pure GEMM), batch-stats BatchNorm, fused add+relu, global avgpool,
+pure GEMM), batch-stats BatchNorm (or per-sample GroupNorm when
+cfg.norm_groups > 0), fused add+relu, global avgpool,
 linear head. All activations are channels-last [N, H, W, C].
 
 Flat-parameter models (models/base.py): conv weights, BN gamma/beta and
@@ -40,7 +41,18 @@ class ResNet(FlatModel):
             self.expansion = 4
         else:
             raise ValueError(self.variant)
+        # 0 = batch-stats BatchNorm; > 0 = GroupNorm with that many
+        # groups in every normalisation layer (same {gamma, beta}
+        # parameters, so the flat layout does not change)
+        self.norm_groups = int(getattr(cfg, "norm_groups", 0))
         super().__init__(cfg, device, compute_dtype)
+        if self.norm_groups > 0:
+            for name, shape, _ in self._specs:
+                if name.endswith(".g") and shape[0] % self.norm_groups:
+                    raise ValueError(
+                        f"norm_groups={self.norm_groups} does not divide "
+                        f"the {shape[0]} channels of layer "
+                        f"'{name[:-2]}' ({self.variant})")
 
     # ------------------------------------------------------------------
     def specs(self):
@@ -87,36 +99,45 @@ class ResNet(FlatModel):
                     off, _ = self._offsets[name]
                     host[off:off + shape[0]].fill_(1.0)
             self.flat.copy_(host.to(self.device))
+        # the base class synced the bf16 shadow before the gammas were
+        # filled in: without this a freshly built GPU model computes its
+        # first forward with gamma = 0 (all-zero logits)
+        self._sync_shadow()
 
     # ------------------------------------------------------------------
-    def _cbr(self, x, conv, bnname, stride=1, pad=1, relu=True):
+    def _conv_norm(self, x, conv, bnname, stride, pad, relu, residual=None):
+        w, g, b = (self.p(f"{conv}.w"), self.p(f"{bnname}.g"),
+                   self.p(f"{bnname}.b"))
+        if self.norm_groups > 0:
+            # conv then per-sample GroupNorm (+residual, +relu fused)
+            return O.conv2d_gn(x, w, g, b, self.norm_groups, stride, pad,
+                               relu=relu, residual=residual)
         # fused conv+BN(+relu): epilogue stats, single norm pass
-        return O.conv2d_bn(x, self.p(f"{conv}.w"), self.p(f"{bnname}.g"),
-                           self.p(f"{bnname}.b"), stride, pad, relu=relu)
+        return O.conv2d_bn(x, w, g, b, stride, pad, relu=relu,
+                           residual=residual)
+
+    def _cbr(self, x, conv, bnname, stride=1, pad=1, relu=True):
+        return self._conv_norm(x, conv, bnname, stride, pad, relu)
 
     def _shortcut(self, x, p, stride):
         if f"{p}.sc.w" in self._offsets:
-            return O.conv2d_bn(x, self.p(f"{p}.sc.w"),
-                               self.p(f"{p}.scbn.g"),
-                               self.p(f"{p}.scbn.b"), stride, 0,
-                               relu=False)
+            return self._conv_norm(x, f"{p}.sc", f"{p}.scbn", stride, 0,
+                                   relu=False)
         return x
 
     def _basic_block(self, x, p, stride):
         h = self._cbr(x, f"{p}.c1", f"{p}.bn1", stride, 1, relu=True)
         sc = self._shortcut(x, p, stride)
-        # final conv+BN fuses the residual add + relu as well
-        return O.conv2d_bn(h, self.p(f"{p}.c2.w"), self.p(f"{p}.bn2.g"),
-                           self.p(f"{p}.bn2.b"), 1, 1, relu=True,
-                           residual=sc)
+        # final conv+norm fuses the residual add + relu as well
+        return self._conv_norm(h, f"{p}.c2", f"{p}.bn2", 1, 1, relu=True,
+                               residual=sc)
 
     def _bottleneck_block(self, x, p, stride):
         h = self._cbr(x, f"{p}.c1", f"{p}.bn1", 1, 0, relu=True)
         h = self._cbr(h, f"{p}.c2", f"{p}.bn2", stride, 1, relu=True)
         sc = self._shortcut(x, p, stride)
-        return O.conv2d_bn(h, self.p(f"{p}.c3.w"), self.p(f"{p}.bn3.g"),
-                           self.p(f"{p}.bn3.b"), 1, 0, relu=True,
-                           residual=sc)
+        return self._conv_norm(h, f"{p}.c3", f"{p}.bn3", 1, 0, relu=True,
+                               residual=sc)
 
     def forward(self, x):
         if self.bottleneck:

@@ -506,6 +506,108 @@ def batchnorm2d(x, gamma, beta, eps: float = 1e-5, relu: bool = False,
     return _BatchNormFn.apply(x, gamma, beta, eps, relu, residual)
 
 
+class _GroupNormFn(torch.autograd.Function):
+    """GroupNorm (NHWC): statistics per (sample, group) over H*W*C/G
+    elements, so a sample's output does not depend on the rest of its
+    batch; parameters are the same per-channel {gamma, beta} as BN.
+    GPU: csrc/hip/groupnorm.hip (slab / split routes, chosen from
+    (H, W, C, G) only); CPU: fp32 oracle. Any shape on CPU; the GPU
+    kernels need C % 8 == 0 and raise otherwise."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, groups: int, eps: float, relu: bool,
+                residual):
+        if x.is_cuda:
+            y, mean, rstd = hip_ops().groupnorm_fwd(x, gamma, beta, groups,
+                                                    eps, relu, residual)
+        else:
+            N, H, W, C = x.shape
+            if groups <= 0 or C % groups:
+                raise ValueError(f"groupnorm: C={C} is not divisible by "
+                                 f"groups={groups}")
+            xg = x.float().reshape(N, H * W, groups, C // groups)
+            mean = xg.mean(dim=(1, 3))
+            var = xg.var(dim=(1, 3), unbiased=False)
+            rstd = (var + eps).rsqrt()
+            xhat = ((xg - mean[:, None, :, None]) * rstd[:, None, :, None]) \
+                .reshape(N, H, W, C)
+            y = xhat * gamma.float() + beta.float()
+            if residual is not None:
+                y = y + residual.float()
+            if relu:
+                y = torch.relu(y)
+            y = y.to(x.dtype)
+        ctx.groups = groups
+        ctx.relu = relu
+        ctx.has_res = residual is not None
+        if relu:
+            ctx.save_for_backward(x, gamma, mean, rstd, y)
+        else:
+            ctx.save_for_backward(x, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mean, rstd = ctx.saved_tensors[:4]
+        yr = ctx.saved_tensors[4] if ctx.relu else None
+        dy = dy.contiguous()
+        dres = None
+        G = ctx.groups
+        if x.is_cuda:
+            if ctx.has_res:
+                # residual grad = relu-masked dy (same mask GN bwd uses)
+                dres = (hip_ops().add_relu_bwd(yr, dy) if yr is not None
+                        else dy)
+            dx, dgamma, dbeta = hip_ops().groupnorm_bwd(x, dy, mean, rstd,
+                                                        gamma, G, yr)
+        else:
+            N, H, W, C = x.shape
+            dyf = dy.float()
+            if yr is not None:
+                dyf = dyf * (yr.float() > 0)
+            if ctx.has_res:
+                dres = dyf.to(x.dtype)
+            m = H * W * (C // G)
+            xg = x.float().reshape(N, H * W, G, C // G)
+            xhat = (xg - mean[:, None, :, None]) * rstd[:, None, :, None]
+            d = (dyf * gamma.float()).reshape(N, H * W, G, C // G)
+            sd = d.sum(dim=(1, 3), keepdim=True)
+            sdx = (d * xhat).sum(dim=(1, 3), keepdim=True)
+            dx = rstd[:, None, :, None] * (d - sd / m - xhat * sdx / m)
+            dx = dx.reshape(N, H, W, C).to(x.dtype)
+            xhat = xhat.reshape(N, H, W, C)
+            dgamma = (dyf * xhat).sum(dim=(0, 1, 2)).to(x.dtype)
+            dbeta = dyf.sum(dim=(0, 1, 2)).to(x.dtype)
+        return dx, dgamma, dbeta, None, None, None, dres
+
+
+def groupnorm2d(x, gamma, beta, groups: int, eps: float = 1e-5,
+                relu: bool = False, residual=None) -> torch.Tensor:
+    """Per-sample GroupNorm with optionally FUSED residual add + relu
+    (one rounding to the output dtype; the relu mask folds into the
+    backward reductions and the residual grad is the masked dy)."""
+    return _GroupNormFn.apply(x, gamma, beta, int(groups), eps, relu,
+                              residual)
+
+
+def conv2d_gn(x, w, gamma, beta, groups: int, stride: int = 1,
+              padding: int = 0, eps: float = 1e-5, relu: bool = True,
+              residual=None) -> torch.Tensor:
+    """conv2d (no bias) -> GroupNorm -> optional residual+relu. The BN
+    path's epilogue-stats fusion emits whole-batch channel partials and
+    cannot serve per-sample statistics, so the conv runs unfused;
+    conv2d still skips the dgrad when x needs no gradient (the stem)."""
+    return groupnorm2d(conv2d(x, w, None, stride, padding), gamma, beta,
+                       groups, eps, relu, residual)
+
+
+def groupnorm_route(H: int, W: int, C: int, groups: int) -> str:
+    """'slab' or 'split': the route the GPU launcher takes for an
+    activation [N, H, W, C] — a function of (H, W, C, groups) and the
+    BFLC_GN_ROUTE knob only, never of N. Host code, needs no GPU."""
+    return hip_ops().groupnorm_route(H, W, C, groups)
+
+
 class _GlobalAvgPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -12,7 +12,10 @@
 // buffers) so the flat parameter vector is exactly {gamma, beta} and
 // committee scoring needs no buffer aggregation — the standard FedBN
 // simplification; deterministic because reductions are fixed-order
-// hierarchical (8-lane tree, chunks ascending), no atomics.
+// hierarchical (8-lane tree, chunks ascending), no atomics. Where a
+// score must not depend on the scorer's batch, groupnorm.hip is the
+// batch-independent alternative with the same parameters
+// (FLConfig.norm_groups > 0).
 
 #include "common.h"
 

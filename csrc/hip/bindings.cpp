@@ -131,6 +131,15 @@ torch::Tensor global_avgpool_bwd(torch::Tensor dy, long H, long W);
 torch::Tensor add_relu_fwd(torch::Tensor a, torch::Tensor b);
 torch::Tensor add_relu_bwd(torch::Tensor y, torch::Tensor dy);
 
+// groupnorm.hip
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> groupnorm_fwd(
+    torch::Tensor x, torch::Tensor gamma, torch::Tensor beta, long groups,
+    double eps, bool relu, c10::optional<torch::Tensor> residual);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> groupnorm_bwd(
+    torch::Tensor x, torch::Tensor dy, torch::Tensor mean, torch::Tensor rstd,
+    torch::Tensor gamma, long groups, c10::optional<torch::Tensor> y_relu);
+std::string groupnorm_route(long H, long W, long C, long groups);
+
 }  // namespace bflc
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -275,4 +284,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("global_avgpool_bwd", &bflc::global_avgpool_bwd);
   m.def("add_relu_fwd", &bflc::add_relu_fwd, "fused residual add + relu");
   m.def("add_relu_bwd", &bflc::add_relu_bwd);
+  m.def("groupnorm_fwd", &bflc::groupnorm_fwd,
+        py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("groups"),
+        py::arg("eps"), py::arg("relu"), py::arg("residual") = py::none(),
+        "(y, mean [N,G], rstd [N,G]) — per-sample GroupNorm, optional "
+        "fused residual add + relu");
+  m.def("groupnorm_bwd", &bflc::groupnorm_bwd, "(dx, dgamma, dbeta)",
+        py::arg("x"), py::arg("dy"), py::arg("mean"), py::arg("rstd"),
+        py::arg("gamma"), py::arg("groups"), py::arg("y_relu") = py::none());
+  m.def("groupnorm_route", &bflc::groupnorm_route,
+        "route groupnorm_fwd/bwd take: slab | split (from H, W, C, groups "
+        "only — never N)",
+        py::arg("H"), py::arg("W"), py::arg("C"), py::arg("groups"));
 }
