@@ -242,6 +242,24 @@ def main():
 
         out[f"train.{name}.bwd_materialized_chain"] = timeit(
             materialized_chain, args.iters)
+        # the data gradient bwd_pooled runs (BFLC_HALO_DGRAD), next to
+        # both of its implementations pinned and the halo kernel alone
+        dimpl = h_ops.pool_dgrad_impl(list(x.shape), list(w.shape), stride,
+                                      pad, want_dx)
+        out[f"train.{name}.bwd_pooled_dgrad_impl"] = dimpl
+        if dimpl == "halo_mfma":
+            for pin in ("implicit_gemm", "halo_mfma"):
+                out[f"train.{name}.bwd_pooled_dgrad_{pin}"] = timeit(
+                    lambda: h_ops.conv2d_relu_pool_bwd(
+                        x, w, yp, idx, dy, stride, pad, True, want_dx, False,
+                        pin), args.iters)
+            out[f"train.{name}.halo_pool_dgrad"] = timeit(
+                lambda: h_ops.halo_pool_dgrad(w, yp, idx, dy), args.iters)
+            # the plane store's cost, against unpool_relu_colsum above as
+            # the other plane producer
+            out[f"train.{name}.halo_pool_dgrad_no_plane"] = timeit(
+                lambda: h_ops.halo_pool_dgrad(w, yp, idx, dy, 0, False),
+                args.iters)
         if not want_dx:
             out[f"train.{name}.thin_fused_wgrad"] = timeit(
                 lambda: h_ops.thin_conv_pool_wgrad_fused(x, yp, idx, dy,

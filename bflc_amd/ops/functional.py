@@ -309,8 +309,11 @@ class _ConvReluPoolFn(torch.autograd.Function):
     backward unpools, ReLU-masks by y_pooled > 0 and sums db in one
     pass, then runs the unchanged conv backward (for a thin first layer
     the same MFMA chains fed straight from the pooled tensors, see
-    thin_conv_pool_wgrad_fused): every gradient is bitwise the two-op
-    path's. With direct_wgrad (BFLC_THIN_DIRECT_WGRAD
+    thin_conv_pool_wgrad_fused; for conv2 at an unsplit batch the data
+    gradient comes from halo_pool_dgrad_kernel, which unpools into LDS,
+    leaves the plane behind for the weight gradient and reads w without
+    the permuted copy, see pool_dgrad_impl): every gradient is bitwise
+    the two-op path's. With direct_wgrad (BFLC_THIN_DIRECT_WGRAD
     =1) a thin first layer goes straight to (dw, db) instead, which is
     faster but sums them in its own order (last-bit differences)."""
 

@@ -116,7 +116,17 @@ std::string conv2d_relu_pool_bwd_route(std::vector<long> x_shape,
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_relu_pool_bwd(
     torch::Tensor x, torch::Tensor w, torch::Tensor y_pooled,
     torch::Tensor idx, torch::Tensor dy_pooled, long stride, long pad,
-    bool want_db, bool want_dx, bool allow_direct);
+    bool want_db, bool want_dx, bool allow_direct, std::string dgrad_impl,
+    long max_blocks);
+std::string pool_dgrad_impl(std::vector<long> x_shape,
+                            std::vector<long> w_shape, long stride, long pad,
+                            bool want_dx);
+long halo_dgrad_group_images_query(std::vector<long> x_shape,
+                                   std::vector<long> w_shape, long stride,
+                                   long pad);
+std::tuple<torch::Tensor, torch::Tensor> halo_pool_dgrad(
+    torch::Tensor w, torch::Tensor y_pooled, torch::Tensor idx,
+    torch::Tensor dy_pooled, long max_blocks, bool store_plane);
 
 // batchnorm.hip
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> batchnorm_fwd(
@@ -268,11 +278,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pad"), py::arg("want_dx"), py::arg("allow_direct") = true);
   m.def("conv2d_relu_pool_bwd", &bflc::conv2d_relu_pool_bwd,
         "(dx, dw, db) of the fused conv + ReLU + pool from its saved "
-        "(x, w, y_pooled, idx)",
+        "(x, w, y_pooled, idx). dgrad_impl pins halo_mfma | implicit_gemm "
+        "('' = pool_dgrad_impl's answer); max_blocks > 0 caps the halo "
+        "kernel's grid",
         py::arg("x"), py::arg("w"), py::arg("y_pooled"), py::arg("idx"),
         py::arg("dy_pooled"), py::arg("stride"), py::arg("pad"),
         py::arg("want_db") = true, py::arg("want_dx") = true,
-        py::arg("allow_direct") = true);
+        py::arg("allow_direct") = true, py::arg("dgrad_impl") = "",
+        py::arg("max_blocks") = 0);
+  m.def("pool_dgrad_impl", &bflc::pool_dgrad_impl,
+        "data gradient the unpool route runs: halo_mfma | implicit_gemm",
+        py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
+        py::arg("pad"), py::arg("want_dx"));
+  m.def("halo_dgrad_group_images", &bflc::halo_dgrad_group_images_query,
+        "images per LDS group of the halo dgrad kernel (0: not its "
+        "geometry)",
+        py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
+        py::arg("pad"));
+  m.def("halo_pool_dgrad", &bflc::halo_pool_dgrad,
+        "the halo dgrad kernel on its geometry alone: (dx, masked "
+        "full-resolution dy plane) from w and the pooled (y, idx, dy); "
+        "store_plane = false skips the plane store (0-size plane)",
+        py::arg("w"), py::arg("y_pooled"), py::arg("idx"),
+        py::arg("dy_pooled"), py::arg("max_blocks") = 0,
+        py::arg("store_plane") = true);
   m.def("batchnorm_fwd", &bflc::batchnorm_fwd,
         py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
         py::arg("relu"), py::arg("residual") = py::none(),

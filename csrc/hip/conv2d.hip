@@ -1015,15 +1015,15 @@ conv2d_fwd_bn(torch::Tensor x, torch::Tensor w, long stride, long pad) {
           stats.second.defined() ? stats.second : none};
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_bwd(
-    torch::Tensor x, torch::Tensor w, torch::Tensor dy, long stride,
-    long pad, c10::optional<torch::Tensor> col_cache, bool want_db,
-    bool want_dx) {
-  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(w); CHECK_CONTIG(dy);
-  auto sh = make_shape(x, w, stride, pad);
-  auto w2 = w.view({(long)sh.Kout, sh.RSC()});
-  auto dy2 = dy.view({sh.M(), (long)sh.Kout});  // NHWC: free view
+namespace {
 
+// The two halves of conv2d_bwd, so that a caller with its own data
+// gradient (the halo route of the pooled backward) runs the weight
+// gradient alone through the same routing.
+torch::Tensor conv_dgrad(const torch::Tensor& x, const torch::Tensor& w,
+                         const torch::Tensor& dy2, const ConvShape& sh,
+                         bool want_dx) {
+  auto w2 = w.view({(long)sh.Kout, sh.RSC()});
   // dgrad. want_dx=false (first-layer convs: the input is data, not an
   // activation) skips the whole dgrad GEMM + col2im — on the ResNet-50
   // stem that is a dcol of M x 147 (~236 MB) plus its col2im pass,
@@ -1076,7 +1076,13 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_bwd(
     }
     HIP_CHECK(hipGetLastError());
   }
+  return dx;
+}
 
+torch::Tensor conv_wgrad(const torch::Tensor& x, const torch::Tensor& w,
+                         const torch::Tensor& dy2, const ConvShape& sh,
+                         const c10::optional<torch::Tensor>& col_cache) {
+  auto w2 = w.view({(long)sh.Kout, sh.RSC()});
   // wgrad: dW[Kout, RSC] = dy2^T @ col. Implicit (col gathered from x
   // inside the GEMM staging) when C % 8 == 0; else a materialized col
   // (reused from the fwd when it produced one).
@@ -1105,13 +1111,27 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_bwd(
       dw.copy_(dwp.slice(1, 0, sh.RSC()));
     }
   }
+  return dw.view(w.sizes());
+}
+
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_bwd(
+    torch::Tensor x, torch::Tensor w, torch::Tensor dy, long stride,
+    long pad, c10::optional<torch::Tensor> col_cache, bool want_db,
+    bool want_dx) {
+  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(w); CHECK_CONTIG(dy);
+  auto sh = make_shape(x, w, stride, pad);
+  auto dy2 = dy.view({sh.M(), (long)sh.Kout});  // NHWC: free view
+  auto dx = conv_dgrad(x, w, dy2, sh, want_dx);
+  auto dw = conv_wgrad(x, w, dy2, sh, col_cache);
 
   // db only when the layer HAS a bias: the conv+BN blocks (every
   // ResNet conv) discard it, and colsum was ~3.3% of a ResNet-20 round
   // spent re-reading all of dy for a dead value
   auto db = want_db ? colsum_bf16(dy2)
                     : torch::empty({0}, dy.options());
-  return {dx, dw.view(w.sizes()), db};
+  return {dx, dw, db};
 }
 
 std::tuple<torch::Tensor, torch::Tensor> maxpool2d_fwd(torch::Tensor x,
@@ -1333,6 +1353,31 @@ ThinFusedPlan thin_fused_plan(const ConvShape& sh) {
   return t;
 }
 
+// db of the pooled backward alone: pool_relu_bwd_colsum's rows, chunks
+// and trees with the plane store left out (the pass
+// thin_conv_pool_wgrad_fused ends with), so db keeps its bits.
+torch::Tensor pool_relu_bwd_db(const torch::Tensor& y_pooled,
+                               const torch::Tensor& idx,
+                               const torch::Tensor& dy_pooled,
+                               const ConvShape& sh) {
+  const long Mpix = sh.M();
+  const long N = sh.Kout;
+  TORCH_CHECK(Mpix * N < (1L << 31), "pool_relu_bwd_db: 32-bit indices");
+  auto db = torch::empty({N}, dy_pooled.options());
+  const ColsumGeom g = colsum_geom(Mpix, N);  // pool_relu_bwd_colsum's
+  auto cpart = torch::empty({g.chunks, N},
+                            dy_pooled.options().dtype(at::kFloat));
+  hipLaunchKernelGGL(pool_relu_bwd_colsum_part_kernel<false>,
+                     dim3(g.cblocks, g.chunks), dim3(256), 0, cur_stream(),
+                     (const bf16*)y_pooled.data_ptr(),
+                     idx.data_ptr<uint8_t>(),
+                     (const bf16*)dy_pooled.data_ptr(), (bf16*)nullptr, Mpix,
+                     N, sh.OH, sh.OW, g.G, g.rows, cpart.data_ptr<float>());
+  HIP_CHECK(hipGetLastError());
+  colsum_finalize(cpart, db);
+  return db;
+}
+
 }  // namespace
 
 torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
@@ -1472,7 +1517,7 @@ std::tuple<torch::Tensor, torch::Tensor> thin_conv_pool_wgrad_fused(
   const long Mpix = sh.M();
   const int N = sh.Kout;
   auto dw = torch::empty({(long)N, 3, 3, 1}, x.options());
-  auto db = torch::empty({(long)N}, x.options());
+  torch::Tensor db;
 
   torch::Tensor part;
   if (t.S > 1)
@@ -1496,18 +1541,7 @@ std::tuple<torch::Tensor, torch::Tensor> thin_conv_pool_wgrad_fused(
     splitk_reduce_plain(part, dw2);
   }
 
-  const ColsumGeom g = colsum_geom(Mpix, N);  // pool_relu_bwd_colsum's
-  auto cpart = torch::empty({g.chunks, (long)N},
-                            x.options().dtype(at::kFloat));
-  hipLaunchKernelGGL(pool_relu_bwd_colsum_part_kernel<false>,
-                     dim3(g.cblocks, g.chunks), dim3(256), 0, cur_stream(),
-                     (const bf16*)y_pooled.data_ptr(),
-                     idx.data_ptr<uint8_t>(),
-                     (const bf16*)dy_pooled.data_ptr(), (bf16*)nullptr, Mpix,
-                     (long)N, sh.OH, sh.OW, g.G, g.rows,
-                     cpart.data_ptr<float>());
-  HIP_CHECK(hipGetLastError());
-  colsum_finalize(cpart, db);
+  db = pool_relu_bwd_db(y_pooled, idx, dy_pooled, sh);
   return {dw, db};
 }
 
@@ -1538,12 +1572,80 @@ std::string conv2d_relu_pool_bwd_route(std::vector<long> x_shape,
                                                              : "unpool";
 }
 
+namespace {
+
+// (dx, masked full-resolution dy plane) of the halo dgrad kernel.
+std::tuple<torch::Tensor, torch::Tensor> halo_pool_dgrad_impl(
+    const torch::Tensor& x_like, const torch::Tensor& w,
+    const torch::Tensor& y_pooled, const torch::Tensor& idx,
+    const torch::Tensor& dy_pooled, const ConvShape& sh, long max_blocks,
+    bool store_plane = true) {
+  auto dyf = store_plane
+                 ? torch::empty({(long)sh.N, (long)sh.OH, (long)sh.OW,
+                                 (long)sh.Kout}, dy_pooled.options())
+                 : torch::empty({0}, dy_pooled.options());
+  auto dx = torch::empty({(long)sh.N, (long)sh.H, (long)sh.W, (long)sh.C},
+                         x_like.options());
+  halo_pool_dgrad_launch(w, y_pooled, idx, dy_pooled,
+                         store_plane ? &dyf : nullptr, dx, sh,
+                         (int)max_blocks);
+  return {dx, dyf};
+}
+
+}  // namespace
+
+// Which data gradient conv2d_relu_pool_bwd's "unpool" route runs:
+// "halo_mfma" (halo_pool_dgrad_kernel on the pooled tensors, which also
+// writes the plane; db from the store-free unpool pass) or
+// "implicit_gemm" (unpool kernel, then conv2d_bwd; also the answer when
+// no dx is wanted). Same bits either way.
+std::string pool_dgrad_impl(std::vector<long> x_shape,
+                            std::vector<long> w_shape, long stride, long pad,
+                            bool want_dx) {
+  const auto sh = make_shape_dims(x_shape, w_shape, stride, pad);
+  return want_dx && halo_dgrad_gate(sh) ? "halo_mfma" : "implicit_gemm";
+}
+
+// Images per LDS group of the halo dgrad kernel (0: not its geometry).
+long halo_dgrad_group_images_query(std::vector<long> x_shape,
+                                   std::vector<long> w_shape, long stride,
+                                   long pad) {
+  return halo_dgrad_group_images(
+      make_shape_dims(x_shape, w_shape, stride, pad));
+}
+
+// The halo dgrad kernel on its geometry alone (tests, op benchmark):
+// (dx, plane). max_blocks > 0 caps the grid; store_plane = false leaves
+// the plane store out (0-size plane), for the measurement of what it
+// costs.
+std::tuple<torch::Tensor, torch::Tensor> halo_pool_dgrad(
+    torch::Tensor w, torch::Tensor y_pooled, torch::Tensor idx,
+    torch::Tensor dy_pooled, long max_blocks, bool store_plane) {
+  CHECK_GPU(w); CHECK_CONTIG(w);
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.dim() == 4,
+              "halo_pool_dgrad: bf16 KRSC w");
+  check_pooled(y_pooled, idx, dy_pooled);
+  const auto sh = make_shape_dims(
+      {y_pooled.size(0), 2 * y_pooled.size(1), 2 * y_pooled.size(2),
+       w.size(3)},
+      w.sizes().vec(), 1, 1);
+  TORCH_CHECK(y_pooled.size(3) == sh.Kout && halo_dgrad_geometry_ok(sh),
+              "halo_pool_dgrad: shape outside the halo kernel's geometry");
+  return halo_pool_dgrad_impl(dy_pooled, w, y_pooled, idx, dy_pooled, sh,
+                              max_blocks, store_plane);
+}
+
 // Backward of conv + bias + ReLU + 2x2/2 maxpool from what the fused
 // forward saved: (dx, dw, db), dx / db 0-size unless wanted.
+// dgrad_impl: "" = what pool_dgrad_impl reports; "halo_mfma" /
+// "implicit_gemm" pin one side of the data gradient (tests, op
+// benchmark; a pinned halo run checks the geometry only). max_blocks > 0
+// caps the halo kernel's grid.
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_relu_pool_bwd(
     torch::Tensor x, torch::Tensor w, torch::Tensor y_pooled,
     torch::Tensor idx, torch::Tensor dy_pooled, long stride, long pad,
-    bool want_db, bool want_dx, bool allow_direct) {
+    bool want_db, bool want_dx, bool allow_direct, std::string dgrad_impl,
+    long max_blocks) {
   CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(w);
   const auto sh = make_shape(x, w, stride, pad);
   TORCH_CHECK(sh.OH % 2 == 0 && sh.OW % 2 == 0 &&
@@ -1551,6 +1653,15 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_relu_pool_bwd(
               y_pooled.size(1) == sh.OH / 2 &&
               y_pooled.size(2) == sh.OW / 2 && y_pooled.size(3) == sh.Kout,
               "conv2d_relu_pool_bwd: pooled shape does not match the conv");
+  TORCH_CHECK(dgrad_impl.empty() || dgrad_impl == "halo_mfma" ||
+                  dgrad_impl == "implicit_gemm",
+              "conv2d_relu_pool_bwd: dgrad_impl is '' | halo_mfma | "
+              "implicit_gemm");
+  const bool force_halo = dgrad_impl == "halo_mfma";
+  TORCH_CHECK(!force_halo || (want_dx && halo_dgrad_geometry_ok(sh) &&
+                              sh.M() * sh.Kout < (1L << 31)),
+              "conv2d_relu_pool_bwd: shape outside the halo dgrad kernel's "
+              "geometry");
   auto none = torch::empty({0}, x.options());
   if (allow_direct && !want_dx && thin_wgrad_eligible(sh)) {
     auto [dw, db] = thin_conv_pool_wgrad(x, y_pooled, idx, dy_pooled,
@@ -1563,6 +1674,19 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_relu_pool_bwd(
     auto [dw, db] = thin_conv_pool_wgrad_fused(x, y_pooled, idx, dy_pooled,
                                                stride, pad);
     return {none, dw.view(w.sizes()), want_db ? db : none};
+  }
+  // conv2's training shape: the data gradient straight from the pooled
+  // tensors, whole images in LDS; the kernel leaves the plane behind for
+  // the unchanged weight gradient. Same bits (halo_pool_dgrad_kernel).
+  if (force_halo ||
+      (dgrad_impl.empty() && want_dx && halo_dgrad_gate(sh))) {
+    check_pooled(y_pooled, idx, dy_pooled);
+    auto db = want_db ? pool_relu_bwd_db(y_pooled, idx, dy_pooled, sh) : none;
+    auto [dx, dyf] = halo_pool_dgrad_impl(x, w, y_pooled, idx, dy_pooled, sh,
+                                          max_blocks);
+    auto dy2 = dyf.view({sh.M(), (long)sh.Kout});
+    auto dw = conv_wgrad(x, w, dy2, sh, c10::nullopt);
+    return {dx, dw, db};
   }
   auto [dyf, db] = pool_relu_bwd_colsum(
       y_pooled, idx, dy_pooled,

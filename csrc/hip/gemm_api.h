@@ -116,6 +116,25 @@ void halo_conv_fwd_pool_launch(const torch::Tensor& x,
                                const torch::Tensor& w2, torch::Tensor& y,
                                const ConvShape& sh, const torch::Tensor* bias,
                                bool relu, uint8_t* idx, int max_blocks);
+// Halo-tile data gradient of that layer's pooled backward
+// (halo_conv.hip): Kout == 64 -> C == 32, 3x3, stride 1, pad 1, even
+// OH/OW. Unpools the pooled (dy, y, idx) into zero-ringed LDS images,
+// writes the masked full-resolution plane dyf [N, OH, OW, Kout] (bitwise
+// pool_relu_bwd_colsum's) for the weight gradient and dx [N, H, W, C]
+// (bitwise the unsplit implicit dgrad's on that plane); w is read as it
+// is, no permuted copy. dyf == nullptr: the plane is not written.
+bool halo_dgrad_geometry_ok(const ConvShape& sh);
+// images a block unpools per group for this geometry (0: not eligible)
+int halo_dgrad_group_images(const ConvShape& sh);
+// geometry && the dgrad plan is unsplit && M * Kout < 2^31 &&
+// BFLC_HALO_DGRAD
+bool halo_dgrad_gate(const ConvShape& sh);
+void halo_pool_dgrad_launch(const torch::Tensor& w,
+                            const torch::Tensor& y_pooled,
+                            const torch::Tensor& idx,
+                            const torch::Tensor& dy_pooled,
+                            torch::Tensor* dyf, torch::Tensor& dx,
+                            const ConvShape& sh, int max_blocks);
 bool gemm_thin_conv_pool_eligible(const ConvShape& sh, long KT);
 bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
                              const torch::Tensor& w2p, torch::Tensor& y,
