@@ -7,7 +7,7 @@ regression harness than rocprof kernel stats (which mix call sites):
 run it before and after a kernel change and diff the per-shape numbers.
 
     python benchmarks/op_bench.py [--iters 50] \
-        [--only conv,score,train,gemm,norm]
+        [--only conv,score,train,gemm,norm,optim]
 """
 import argparse
 import json
@@ -96,13 +96,17 @@ NORMS = [
     ("thr.128k", 256, 32, 64, 8),
 ]
 
+# (name, P) flat master sizes of the fused optimizer steps: FEMNIST CNN,
+# ResNet-20, ResNet-50
+OPTIMS = [("fe", 421_000), ("r20", 272_000), ("r50", 25_600_000)]
+
 COPY_BW = 6.29e12  # measured device copy bandwidth, bytes/s
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--only", default="conv,score,train,gemm,norm",
+    ap.add_argument("--only", default="conv,score,train,gemm,norm,optim",
                     help="comma-separated sections to run")
     args = ap.parse_args()
     only = set(args.only.split(","))
@@ -324,6 +328,38 @@ def main():
         os.environ.pop("BFLC_GN_ROUTE", None)
         if saved is not None:
             os.environ["BFLC_GN_ROUTE"] = saved
+
+    # fused master-weight steps: the legacy sgd_master_ (12 B/element:
+    # p read + write, bf16 g read, bf16 shadow write), the extended
+    # sgdm step (+8 B with momentum, +4 B with the proximal term) and
+    # the clip pair (one 2 B/element pass + a one-block final)
+    for name, n in (OPTIMS if "optim" in only else []):
+        h_ops = O.hip_ops()
+        p = torch.randn(n, device=dev)
+        sh = p.to(torch.bfloat16)
+        g = (torch.randn(n, device=dev) * 1e-3).to(torch.bfloat16)
+        buf = torch.zeros(n, device=dev)
+        p0 = p.clone()
+        one = torch.zeros(1, device=dev)
+        lr_dev = torch.full((1,), 1e-6, device=dev)
+        coef = torch.ones(2, device=dev)
+        rows = [
+            ("sgd_master_", 12, lambda: h_ops.sgd_master_(p, sh, g, 1e-6)),
+            ("sgdm.plain", 12, lambda: O.sgdm_step_(
+                p, sh, g, one, one, lr_dev, coef, 0.0, False, 0.0, 0.0)),
+            ("sgdm.mom", 20, lambda: O.sgdm_step_(
+                p, sh, g, buf, one, lr_dev, coef, 0.9, False, 0.0, 0.0)),
+            ("sgdm.mom_nest_wd", 20, lambda: O.sgdm_step_(
+                p, sh, g, buf, one, lr_dev, coef, 0.9, True, 1e-4, 0.0)),
+            ("sgdm.mom_nest_wd_prox", 24, lambda: O.sgdm_step_(
+                p, sh, g, buf, p0, lr_dev, coef, 0.9, True, 1e-4, 0.01)),
+            ("clip_coef_pair", 2, lambda: O.grad_clip_coef_(g, 1.0, coef)),
+        ]
+        for tag, bytes_per, fn in rows:
+            t = timeit(fn, args.iters)
+            out[f"optim.{name}.{tag}"] = t
+            out[f"optim.{name}.{tag}.GBps"] = bytes_per * n / (t * 1e-6) / 1e9
+        coef.fill_(1.0)
 
     print(json.dumps({"unit": "us_per_call", "ops": out}, indent=1))
 

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import dataclasses
 import json
+import math
 from dataclasses import dataclass
 from typing import Any, Dict
 
@@ -43,6 +44,21 @@ class FLConfig:
     norm_groups: int = 0           # ResNets: 0 = batch-stats BatchNorm,
                                    # > 0 = GroupNorm with that many groups
 
+    # --- extended local SGD (all defaults mean "off": the legacy
+    # sgd_master_ step). Only the LOCAL step is affected; delta
+    # extraction, candidates, the server apply and the ledger keep the
+    # constant `learning_rate` (DESIGN.md "Local optimizer") ---
+    momentum: float = 0.0          # heavy ball, dampening 0 (torch.optim.SGD)
+    nesterov: bool = False         # needs momentum > 0
+    weight_decay: float = 0.0      # L2 added to the gradient, whole vector
+    prox_mu: float = 0.0           # FedProx: + mu * (p - p_global)
+    clip_norm: float = 0.0         # global L2 clip of the loss gradient; 0 = off
+    lr_schedule: str = "constant"  # constant | step | cosine (by ledger epoch)
+    lr_gamma: float = 0.1          # step: lr * gamma ** (epoch // lr_step_rounds)
+    lr_step_rounds: int = 0
+    lr_total_rounds: int = 0       # cosine horizon; 0 means max_epoch
+    lr_min: float = 0.0            # cosine floor
+
     # --- sharding ---
     partition: str = "iid"         # iid | dirichlet (non-IID)
     dirichlet_alpha: float = 0.3
@@ -69,6 +85,51 @@ class FLConfig:
             raise ValueError("needed_update_count exceeds trainer count")
         if self.norm_groups < 0:
             raise ValueError("norm_groups must be >= 0")
+        for name in ("momentum", "weight_decay", "prox_mu", "clip_norm",
+                     "lr_gamma", "lr_step_rounds", "lr_total_rounds",
+                     "lr_min"):
+            if getattr(self, name) < 0:
+                raise ValueError(f"{name} must be >= 0")
+        if self.nesterov and not self.momentum > 0:
+            raise ValueError("nesterov needs momentum > 0")
+        if self.lr_schedule not in ("constant", "step", "cosine"):
+            raise ValueError(f"unknown lr_schedule {self.lr_schedule!r}")
+        if self.lr_schedule == "step" and not self.lr_step_rounds > 0:
+            raise ValueError("lr_schedule='step' needs lr_step_rounds > 0")
+        if self.extended_sgd and self.optimizer == "adam":
+            raise ValueError(
+                "momentum / weight_decay / prox_mu / clip_norm / lr schedule "
+                "fields extend optimizer='sgd' only")
+
+    # ------------------------------------------------------------------
+    _EXTENDED_DEFAULTS = dict(
+        momentum=0.0, nesterov=False, weight_decay=0.0, prox_mu=0.0,
+        clip_norm=0.0, lr_schedule="constant", lr_gamma=0.1,
+        lr_step_rounds=0, lr_total_rounds=0, lr_min=0.0)
+
+    @property
+    def extended_sgd(self) -> bool:
+        """True as soon as any extended-SGD field differs from its
+        default: the local step then runs the sgdm kernels."""
+        return any(getattr(self, k) != v
+                   for k, v in self._EXTENDED_DEFAULTS.items())
+
+    def local_lr(self, epoch: int) -> float:
+        """Local step size at a ledger epoch (Python doubles; a pure
+        function of the config, so it is identical on every rank and
+        needs no checkpoint state). The protocol's `learning_rate`
+        (delta scale, server apply, ledger) is NOT scheduled."""
+        lr, e = float(self.learning_rate), int(epoch)
+        if self.lr_schedule == "step":
+            return lr * float(self.lr_gamma) ** (e // self.lr_step_rounds)
+        if self.lr_schedule == "cosine":
+            T = self.lr_total_rounds or self.max_epoch
+            if T <= 0:
+                return lr
+            lo = float(self.lr_min)
+            return lo + 0.5 * (lr - lo) * (
+                1.0 + math.cos(math.pi * min(e, T) / T))
+        return lr
 
     # ------------------------------------------------------------------
     @classmethod

@@ -132,6 +132,24 @@ class FLEngine:
         self._round = 0
         self.metrics = JsonlLogger(metrics_path, rank=self.rank)
 
+        # which fused local step this engine runs: the legacy
+        # sgd_master_ step, the extended sgdm kernels (momentum / weight
+        # decay / FedProx / clip / scheduled lr — cfg.extended_sgd) or
+        # Adam. Public so tests cannot pass through the wrong path.
+        self.local_optimizer = ("adam" if cfg.optimizer == "adam" else
+                                "sgdm" if cfg.extended_sgd else "sgd_legacy")
+        # sgdm: ONE device learning rate, refilled from
+        # cfg.local_lr(epoch) at the top of every round on the main
+        # stream (before the client streams fork); every captured step
+        # reads it, so a schedule never forces a recapture. The
+        # proximal anchor is global_flat itself (address-stable).
+        self._lr_dev: Optional[torch.Tensor] = None
+        self._eager_sgdm = None
+        if self.local_optimizer == "sgdm":
+            self._lr_dev = torch.full(
+                (1,), cfg.local_lr(self.ledger.epoch), dtype=torch.float32,
+                device=self.device)
+
         # hipGraph-captured train step (fl/graphs.py): replay one
         # captured kernel DAG per minibatch instead of relaunching
         # ~dozens of kernels. SGD-only; falls back to eager on CPU, on
@@ -190,6 +208,22 @@ class FLEngine:
         return order[: self.cfg.needed_update_count]
 
     # ------------------------------------------------------------------
+    def _graph_optimizer(self) -> dict:
+        """Optimizer arguments of the graph classes (fl/graphs.py)."""
+        if self.local_optimizer == "sgdm":
+            return dict(optimizer="sgdm", sgdm_cfg=self.cfg,
+                        lr_dev=self._lr_dev, p0=self.global_flat)
+        return dict(optimizer=self.cfg.optimizer)
+
+    def _sgdm_state(self):
+        """Extended-SGD state of the eager (ungraphed) local step."""
+        if self._eager_sgdm is None:
+            from bflc_amd.models.base import SGDMState
+            self._eager_sgdm = SGDMState.for_model(
+                self.cfg, self.model, self._lr_dev, self.global_flat)
+        return self._eager_sgdm
+
+    # ------------------------------------------------------------------
     def _graphed_stepper(self, shard: Shard, bs: int):
         """Lazily capture the train-step hipGraph (fl/graphs.py), one
         stepper per batch shape (heterogeneous shard sizes each get
@@ -203,8 +237,8 @@ class FLEngine:
         try:
             from bflc_amd.fl.graphs import GraphedTrainStep
             st = GraphedTrainStep(self.model, self.cfg.learning_rate, xb,
-                                  yb, optimizer=self.cfg.optimizer,
-                                  pool=self._graph_pool)
+                                  yb, pool=self._graph_pool,
+                                  **self._graph_optimizer())
             if self._graph_pool is None:
                 self._graph_pool = st.pool()
             self._steppers[key] = st
@@ -270,8 +304,8 @@ class FLEngine:
             g = GraphedLocalTrain(model, self.cfg.learning_rate,
                                   shard.x, shard.y, self.cfg.batch_size,
                                   self.cfg.local_epochs,
-                                  optimizer=self.cfg.optimizer,
-                                  pool=self._capture_pool(client))
+                                  pool=self._capture_pool(client),
+                                  **self._graph_optimizer())
             self._note_pool(client, g)
         except Exception as e:
             warnings.warn(f"whole-train graph capture failed for client "
@@ -309,6 +343,10 @@ class FLEngine:
             m = torch.zeros_like(self.global_flat)
             v = torch.zeros_like(self.global_flat)
             step = 0
+        sgdm = None
+        if self.local_optimizer == "sgdm" and stepper is None:
+            sgdm = self._sgdm_state()
+            sgdm.reset()  # fresh momentum per client, as Adam's (m, v)
         if stepper is not None:
             stepper.cost.zero_()
             stepper.reset_state()  # fresh Adam (m, v, step) per client
@@ -331,6 +369,8 @@ class FLEngine:
                     if cfg.optimizer == "adam":
                         step += 1
                         self.model.adam_step(m, v, step, cfg.learning_rate)
+                    elif sgdm is not None:
+                        self.model.sgdm_step(sgdm)
                     else:
                         self.model.sgd_step(cfg.learning_rate)
                     cost_accum += loss.detach()
@@ -471,6 +511,11 @@ class FLEngine:
                 "main.py:251-252)")
         epoch = led.epoch
         t0 = time.perf_counter()
+        # only the LOCAL step size is scheduled; delta extraction,
+        # candidates and the server apply keep cfg.learning_rate
+        local_lr = cfg.local_lr(epoch)
+        if self._lr_dev is not None:
+            self._lr_dev.fill_(local_lr)
 
         # ---- phase T: local training on designated submitters ----------
         # Concurrent path: each local trainer's whole-training graph
@@ -716,7 +761,7 @@ class FLEngine:
             n_selected=K, samples_trained=samples_trained, test_acc=acc)
         self.metrics.log("round", stats,
                          selected=[o for o, _ in decision.selected],
-                         bad_signatures=n_bad_sig)
+                         bad_signatures=n_bad_sig, local_lr=local_lr)
         return stats
 
     # ------------------------------------------------------------------

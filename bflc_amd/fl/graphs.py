@@ -34,6 +34,14 @@ Adam-on-GPU-fp32 (no bf16 shadow) stays eager: only the master+shadow
 kernel has the device-step variant, and fp32 compute is a test-only
 configuration.
 
+The extended SGD step (``optimizer="sgdm"``: momentum, weight decay,
+FedProx, clipping, scheduled lr) captures the same way: its learning
+rate and clip coefficient are DEVICE floats (csrc/hip/optimizer.hip), so
+the caller refills ``lr_dev`` between replays and the same graph runs at
+the new step size. The graph classes own the momentum buffer and the
+coefficient; ``lr_dev`` and the proximal anchor ``p0`` are the caller's
+and must keep their addresses.
+
 Capture executes real kernels, so construction MUTATES the weights —
 callers build the stepper before loading the round's global weights
 (engine.py does this), or snapshot/restore around construction.
@@ -48,13 +56,23 @@ from __future__ import annotations
 import torch
 
 
+def _sgdm_state(model, sgdm_cfg, lr_dev, p0):
+    """Graph-owned extended-SGD state: fresh buf + coef_dev, the
+    caller's lr_dev / p0 (fixed addresses, baked into the capture)."""
+    from bflc_amd.models.base import SGDMState
+    if sgdm_cfg is None or lr_dev is None:
+        raise ValueError("optimizer='sgdm' needs sgdm_cfg and lr_dev")
+    return SGDMState.for_model(sgdm_cfg, model, lr_dev, p0)
+
+
 class GraphedTrainStep:
     """One captured (forward, backward, fused-optimizer) step over
     static input buffers; ``step()`` copies a batch in and replays."""
 
     def __init__(self, model, lr: float, x_proto: torch.Tensor,
                  y_proto: torch.Tensor, optimizer: str = "sgd",
-                 warmup: int = 2, pool=None) -> None:
+                 warmup: int = 2, pool=None, sgdm_cfg=None, lr_dev=None,
+                 p0=None) -> None:
         self.model = model
         self.optimizer = optimizer
         self.sx = torch.empty_like(x_proto)
@@ -74,6 +92,8 @@ class GraphedTrainStep:
                                       dtype=torch.int32)
             self.bc = torch.zeros(2, device=model.device,
                                   dtype=torch.float32)
+        elif optimizer == "sgdm":
+            self.sgdm = _sgdm_state(model, sgdm_cfg, lr_dev, p0)
         elif optimizer != "sgd":
             raise ValueError(optimizer)
         self._lr = float(lr)
@@ -101,6 +121,8 @@ class GraphedTrainStep:
         if self.optimizer == "adam":
             self.model.adam_step_graph(self.m, self.v, self.step_t,
                                        self.bc, self._lr)
+        elif self.optimizer == "sgdm":
+            self.model.sgdm_step(self.sgdm)
         else:
             self.model.sgd_step(self._lr)
 
@@ -117,6 +139,8 @@ class GraphedTrainStep:
             self.m.zero_()
             self.v.zero_()
             self.step_t.zero_()
+        elif self.optimizer == "sgdm":
+            self.sgdm.reset()
 
     def pool(self):
         return self.graph.pool()
@@ -144,7 +168,7 @@ class GraphedLocalTrain:
     def __init__(self, model, lr: float, shard_x: torch.Tensor,
                  shard_y: torch.Tensor, batch_size: int,
                  local_epochs: int, optimizer: str = "sgd",
-                 pool=None) -> None:
+                 pool=None, sgdm_cfg=None, lr_dev=None, p0=None) -> None:
         self.model = model
         self.optimizer = optimizer
         self.cost = torch.zeros((), device=model.device,
@@ -162,6 +186,8 @@ class GraphedLocalTrain:
                                       dtype=torch.int32)
             self.bc = torch.zeros(2, device=model.device,
                                   dtype=torch.float32)
+        elif optimizer == "sgdm":
+            self.sgdm = _sgdm_state(model, sgdm_cfg, lr_dev, p0)
         elif optimizer != "sgd":
             raise ValueError(optimizer)
         self._lr = float(lr)
@@ -185,6 +211,8 @@ class GraphedLocalTrain:
         if self.optimizer == "adam":
             self.model.adam_step_graph(self.m, self.v, self.step_t,
                                        self.bc, self._lr)
+        elif self.optimizer == "sgdm":
+            self.model.sgdm_step(self.sgdm)
         else:
             self.model.sgd_step(self._lr)
 
@@ -208,6 +236,8 @@ class GraphedLocalTrain:
             self.m.zero_()
             self.v.zero_()
             self.step_t.zero_()
+        elif self.optimizer == "sgdm":
+            self.sgdm.reset()
         self.graph.replay()
         return self.cost
 

@@ -14,11 +14,56 @@ main.py:153-154).
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from bflc_amd.ops import functional as O
+
+
+@dataclass
+class SGDMState:
+    """What FlatModel.sgdm_step needs besides the gradient: the
+    momentum buffer, the DEVICE learning rate and clip coefficient (so a
+    captured step replays under a refilled lr), the FedProx anchor and
+    the hyper-parameters. `buf` is a 1-element dummy at momentum == 0
+    and `p0` may be one at prox_mu == 0: the kernel touches neither."""
+    buf: torch.Tensor
+    lr_dev: torch.Tensor
+    coef_dev: torch.Tensor
+    p0: torch.Tensor
+    momentum: float = 0.0
+    nesterov: bool = False
+    weight_decay: float = 0.0
+    prox_mu: float = 0.0
+    clip_norm: float = 0.0
+
+    @classmethod
+    def for_model(cls, cfg, model: "FlatModel", lr_dev: torch.Tensor,
+                  p0: Optional[torch.Tensor] = None) -> "SGDMState":
+        """Fresh state owning buf and coef_dev; lr_dev and p0 belong to
+        the caller (the engine: one lr_dev, p0 = its global model)."""
+        n = model.numel if cfg.momentum > 0 else 1
+        buf = torch.zeros(n, dtype=torch.float32, device=model.device)
+        # (coef, sum of squares); coef stays 1 with clipping off
+        coef = torch.tensor([1.0, 0.0], dtype=torch.float32,
+                            device=model.device)
+        if p0 is None:
+            if cfg.prox_mu > 0:
+                raise ValueError("prox_mu > 0 needs the proximal anchor p0")
+            p0 = buf[:1]
+        return cls(buf=buf, lr_dev=lr_dev, coef_dev=coef, p0=p0,
+                   momentum=float(cfg.momentum), nesterov=bool(cfg.nesterov),
+                   weight_decay=float(cfg.weight_decay),
+                   prox_mu=float(cfg.prox_mu),
+                   clip_norm=float(cfg.clip_norm))
+
+    def reset(self) -> None:
+        """Fresh momentum for a new client / round (on the current
+        stream), as Adam's (m, v) are."""
+        if self.momentum > 0:
+            self.buf.zero_()
 
 
 class FlatModel:
@@ -154,6 +199,20 @@ class FlatModel:
             with torch.no_grad():
                 self.flat.add_(g.float(), alpha=-lr)
                 self.cflat.data.copy_(self.flat.to(self.compute_dtype))
+
+    def sgdm_step(self, state: SGDMState) -> None:
+        """Extended SGD (momentum / nesterov / weight decay / FedProx /
+        global-norm clip, device-resident lr) in one fused pass over the
+        master (+ shadow): ops/functional.py sgdm_step_. hipGraph-
+        capturable as is — nothing host-side is baked in but the
+        hyper-parameters that never change within a run."""
+        g = self.grad_flat()
+        if state.clip_norm > 0:
+            O.grad_clip_coef_(g, state.clip_norm, state.coef_dev)
+        shadow = None if self.cflat is self.flat else self.cflat.data
+        O.sgdm_step_(self.flat.detach(), shadow, g, state.buf, state.p0,
+                     state.lr_dev, state.coef_dev, state.momentum,
+                     state.nesterov, state.weight_decay, state.prox_mu)
 
     def adam_step(self, m: torch.Tensor, v: torch.Tensor, step: int,
                   lr: float) -> None:

@@ -5,6 +5,7 @@ from bflc_amd.ops.functional import (accuracy, accuracy_t, adam_step_,
                                      global_avgpool, add_relu,
                                      hip_available, hip_ops, linear,
                                      maxpool2d, relu, sgd_step_,
+                                     sgdm_step_, grad_clip_coef_,
                                      softmax_cross_entropy, weighted_fedavg)
 
 __all__ = [
@@ -12,5 +13,6 @@ __all__ = [
     "batchnorm2d", "relu",
     "add_relu", "maxpool2d", "global_avgpool", "softmax_cross_entropy",
     "accuracy", "accuracy_t", "axpy_", "sgd_step_", "adam_step_",
+    "sgdm_step_", "grad_clip_coef_",
     "weighted_fedavg", "hip_ops", "hip_available",
 ]

@@ -725,6 +725,101 @@ def sgd_step_(flat_param: torch.Tensor, flat_grad: torch.Tensor,
         flat_param.add_(flat_grad, alpha=-lr)
 
 
+def grad_sumsq_geom(n: int):
+    """(blocks, longest lane chain in elements, adds after the lane
+    chain) of the sum-of-squares kernels at n elements — a function of n
+    alone, answered by the extension's host code (no GPU needed)."""
+    return tuple(hip_ops().grad_sumsq_geom(int(n)))
+
+
+def sgdm_step_geom(n: int):
+    """(blocks, threads, elements per thread per grid-stride pass) of
+    the fused sgdm update at n elements (host code, no GPU needed)."""
+    return tuple(hip_ops().sgdm_step_geom(int(n)))
+
+
+def grad_clip_coef_(g: torch.Tensor, clip: float,
+                    out: torch.Tensor) -> None:
+    """out[0] = min(1, clip / (||g||_2 + 1e-6)) — the coefficient of
+    torch.nn.utils.clip_grad_norm_ — as a DEVICE float (no host sync);
+    0 when the sum of squares is not finite, which makes sgdm_step_ skip
+    the step. out may hold a second float, which receives sum(g^2).
+
+    GPU: grad_sumsq_part + grad_clip_final (csrc/hip/optimizer.hip),
+    fp32 with a fixed summation order. CPU oracle: the same formula with
+    an fp32 sum in torch's order."""
+    if not clip > 0:
+        raise ValueError("clip must be > 0")
+    if g.is_cuda:
+        hip_ops().grad_clip_coef_(g, float(clip), out)
+        return
+    with torch.no_grad():
+        ss = g.float().square().sum()
+        if bool(torch.isfinite(ss)):
+            coef = torch.clamp(
+                torch.tensor(float(clip), dtype=torch.float32)
+                / (ss.sqrt() + 1e-6), max=1.0)
+        else:
+            coef = torch.zeros((), dtype=torch.float32)
+        out[0] = coef
+        if out.numel() > 1:
+            out[1] = ss
+
+
+def sgdm_step_(p: torch.Tensor, shadow: Optional[torch.Tensor],
+               g: torch.Tensor, buf: torch.Tensor, p0: torch.Tensor,
+               lr_dev: torch.Tensor, coef_dev: torch.Tensor,
+               momentum: float, nesterov: bool, wd: float,
+               mu: float) -> None:
+    """Fused extended-SGD update of the fp32 master `p` (and its bf16
+    `shadow`, or None) in place; `lr_dev` and `coef_dev` are 1-element
+    fp32 tensors on p's device, so a captured graph replays under a
+    refilled learning rate.
+
+    Operation order (identical in sgdm_master_dev_kernel,
+    csrc/hip/optimizer.hip): every input is widened exactly to fp64, the
+    chain runs in fp64, and p and buf are each rounded to fp32 once:
+
+        if coef == 0: return          (non-finite gradient: step skipped)
+        g = coef * grad               (the clip scales the loss gradient only)
+        g = fma(wd, p, g)             only if wd != 0
+        g = fma(mu, p - p0, g)        only if mu != 0 (p0 untouched otherwise)
+        b = fma(mom, buf, g); buf = fp32(b)    only if momentum != 0
+        d = nesterov ? fma(mom, b, g) : b      (d = g without momentum)
+        p = fp32(fma(-lr, d, p)); shadow = bf16(p)
+
+    The CPU oracle below evaluates the same chain with separate fp64
+    multiply and add; against the kernel's fused fp64 fma that can move
+    a stored fp32 value only when the fp64 result sits within 2^-53 of a
+    rounding boundary. `buf` is read and written only at momentum != 0
+    and `p0` read only at mu != 0 — pass any tensor otherwise."""
+    if nesterov and not momentum > 0:
+        raise ValueError("nesterov needs momentum > 0")
+    if p.is_cuda:
+        hip_ops().sgdm_master_dev_(p, shadow, g, buf, p0, lr_dev, coef_dev,
+                                   float(momentum), bool(nesterov),
+                                   float(wd), float(mu))
+        return
+    with torch.no_grad():
+        coef = coef_dev[0].double()
+        if float(coef) == 0.0:
+            return
+        pd = p.double()
+        gd = coef * g.double()
+        if wd != 0:
+            gd = gd + float(wd) * pd
+        if mu != 0:
+            gd = gd + float(mu) * (pd - p0.double())
+        d = gd
+        if momentum != 0:
+            b = float(momentum) * buf.double() + gd
+            buf.copy_(b.float())
+            d = gd + float(momentum) * b if nesterov else b
+        p.copy_((pd - lr_dev[0].double() * d).float())
+        if shadow is not None:
+            shadow.copy_(p.to(shadow.dtype))
+
+
 def adam_step_(flat_param: torch.Tensor, flat_grad: torch.Tensor,
                m: torch.Tensor, v: torch.Tensor, step: int, lr: float,
                beta1: float = 0.9, beta2: float = 0.999,

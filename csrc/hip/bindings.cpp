@@ -33,6 +33,15 @@ torch::Tensor relu_bwd(torch::Tensor y, torch::Tensor dy);
 std::tuple<torch::Tensor, torch::Tensor> relu_bwd_colsum(
     const torch::Tensor& y, const torch::Tensor& dy);
 
+// optimizer.hip
+std::tuple<long, long, long> grad_sumsq_geom_query(long n);
+std::tuple<long, long, long> sgdm_step_geom_query(long n);
+void grad_clip_coef_(torch::Tensor g, double clip, torch::Tensor out);
+void sgdm_master_dev_(torch::Tensor p, c10::optional<torch::Tensor> shadow,
+                      torch::Tensor g, torch::Tensor buf, torch::Tensor p0,
+                      torch::Tensor lr_dev, torch::Tensor coef_dev,
+                      double momentum, bool nesterov, double wd, double mu);
+
 // softmax_ce.hip
 std::tuple<torch::Tensor, torch::Tensor> softmax_ce_fwd(torch::Tensor logits,
                                                         torch::Tensor target);
@@ -171,6 +180,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "candidate load (replaces copy+axpy+set_flat)");
   m.def("delta_extract_", &bflc::delta_extract_,
         "out = (global - w)/lr: one-pass pseudo-gradient extraction");
+  m.def("grad_sumsq_geom", &bflc::grad_sumsq_geom_query,
+        "sum-of-squares geometry of an n-element gradient: (blocks, "
+        "longest lane chain in elements, adds after the lane chain)",
+        py::arg("n"));
+  m.def("sgdm_step_geom", &bflc::sgdm_step_geom_query,
+        "launch of sgdm_master_dev_ at n elements: (blocks, threads, "
+        "elements per thread per grid-stride pass)",
+        py::arg("n"));
+  m.def("grad_clip_coef_", &bflc::grad_clip_coef_,
+        "out[0] = min(1, clip / (||g||_2 + 1e-6)), 0 if the norm is not "
+        "finite; out[1] = sum(g^2) when out has two elements",
+        py::arg("g"), py::arg("clip"), py::arg("out"));
+  m.def("sgdm_master_dev_", &bflc::sgdm_master_dev_,
+        "fused SGD (momentum / nesterov / weight decay / FedProx / clip "
+        "coefficient) on the fp32 master (+ bf16 shadow); lr and coef are "
+        "device floats",
+        py::arg("p"), py::arg("shadow"), py::arg("g"), py::arg("buf"),
+        py::arg("p0"), py::arg("lr_dev"), py::arg("coef_dev"),
+        py::arg("momentum"), py::arg("nesterov"), py::arg("wd"),
+        py::arg("mu"));
   m.def("relu_fwd", &bflc::relu_fwd);
   m.def("relu_bwd", &bflc::relu_bwd);
   m.def("relu_bwd_colsum", &bflc::relu_bwd_colsum,
