@@ -175,6 +175,29 @@ def main():
                 lambda: h_ops.conv2d_relu_pool_fwd(x, w, b, stride, pad, 0,
                                                    "halo_mfma"), args.iters)
 
+    # the grad-free stack at the scoring shard: the two fused calls
+    # (thin conv1 then halo conv2) vs the one kernel that computes
+    # conv2's input in LDS (bitwise equal), both pinned, and the default
+    # route. score.fe.conv1.fused above is conv1's pooled forward alone.
+    if "score" in only:
+        h_ops = O.hip_ops()
+        n = SCORE_CONVS[0][1]
+        x = torch.randn(n, 28, 28, 1, device=dev, dtype=torch.bfloat16)
+        w1 = torch.randn(32, 3, 3, 1, device=dev, dtype=torch.bfloat16) * 0.3
+        b1 = torch.randn(32, device=dev, dtype=torch.bfloat16)
+        w2 = torch.randn(64, 3, 3, 32, device=dev, dtype=torch.bfloat16) * .05
+        b2 = torch.randn(64, device=dev, dtype=torch.bfloat16)
+        out["score.fe.stack.route"] = h_ops.conv_relu_pool_stack_route(
+            list(x.shape), list(w1.shape), list(w2.shape))
+        for impl in ("two_call", "halo_stack", ""):
+            out[f"score.fe.stack.{impl or 'default'}"] = timeit(
+                lambda: h_ops.conv_relu_pool_stack_fwd(x, w1, b1, w2, b2, 0,
+                                                       impl), args.iters)
+        # bytes the stack has to move: pixels in, pooled output out
+        need = n * 28 * 28 * 2 + n * 7 * 7 * 64 * 2
+        out["score.fe.stack.halo_stack_necessary_GBps"] = (
+            need / out["score.fe.stack.halo_stack"] / 1e3)
+
     # training conv + ReLU + 2x2 pool stages: the two-op forward (conv
     # writes the full plane, pool reads it back) vs the fused one that
     # also emits the argmax plane, and the old backward chain (unpool,

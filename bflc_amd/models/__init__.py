@@ -59,10 +59,12 @@ class FemnistCNN(FlatModel):
                 ("f2w", (128, c.n_class), "xavier"), ("f2b", (c.n_class,), "zeros")]
 
     def forward(self, x):
-        # conv + ReLU + 2x2 pool: one fused kernel per stage when grad
-        # mode is off (scoring / eval), the two-op sequence in training
-        h = O.conv2d_relu_pool(x, self.p("c1w"), self.p("c1b"), 1, 1)
-        h = O.conv2d_relu_pool(h, self.p("c2w"), self.p("c2b"), 1, 1)
+        # conv + ReLU + 2x2 pool twice: with grad mode off (scoring /
+        # eval) one kernel for both stages where the stack route takes
+        # the batch, else one fused kernel per stage; training keeps a
+        # fused forward + backward per stage
+        h = O.conv_relu_pool_stack(x, self.p("c1w"), self.p("c1b"),
+                                   self.p("c2w"), self.p("c2b"))
         h = h.reshape(h.shape[0], -1)
         h = O.linear(h, self.p("f1w"), self.p("f1b"), relu=True)
         return O.linear(h, self.p("f2w"), self.p("f2b"))

@@ -2,6 +2,7 @@ from bflc_amd.ops import functional
 from bflc_amd.ops.functional import (accuracy, accuracy_t, adam_step_,
                                      axpy_, batchnorm2d, conv2d, conv2d_bn,
                                      conv2d_relu_pool,
+                                     conv_relu_pool_stack,
                                      global_avgpool, add_relu,
                                      hip_available, hip_ops, linear,
                                      maxpool2d, relu, sgd_step_,
@@ -10,7 +11,7 @@ from bflc_amd.ops.functional import (accuracy, accuracy_t, adam_step_,
 
 __all__ = [
     "functional", "linear", "conv2d", "conv2d_bn", "conv2d_relu_pool",
-    "batchnorm2d", "relu",
+    "conv_relu_pool_stack", "batchnorm2d", "relu",
     "add_relu", "maxpool2d", "global_avgpool", "softmax_cross_entropy",
     "accuracy", "accuracy_t", "axpy_", "sgd_step_", "adam_step_",
     "sgdm_step_", "grad_clip_coef_",

@@ -377,6 +377,30 @@ def conv2d_relu_pool(x, w, b=None, stride: int = 1,
     return maxpool2d(conv2d(x, w, b, stride, padding, relu=True), 2)
 
 
+def conv_relu_pool_stack(x, w1, b1, w2, b2) -> torch.Tensor:
+    """Two conv3x3(stride 1, pad 1) + ReLU + 2x2 pool stages:
+    conv2d_relu_pool(conv2d_relu_pool(x, w1, b1, 1, 1), w2, b2, 1, 1).
+
+    With grad mode off, on a GPU, where conv_relu_pool_stack_route says
+    "halo_stack" (a thin first layer into the halo-tile second one, see
+    csrc/hip/halo_conv.hip) the pair is ONE kernel: each block computes
+    its conv2 input images from the raw pixels straight into LDS, so the
+    pooled first-layer activation is never written to HBM and read back.
+    The result is bitwise the two calls. Training, the CPU, every other
+    shape and BFLC_FUSED_POOL=0 run the two calls; BFLC_HALO_STACK=0
+    (read once per process) closes the route for A/B runs.
+    """
+    import os
+    if x.is_cuda and not torch.is_grad_enabled() and \
+            os.environ.get("BFLC_FUSED_POOL", "1") == "1" and \
+            b1 is not None and b2 is not None and \
+            hip_ops().conv_relu_pool_stack_route(
+                list(x.shape), list(w1.shape), list(w2.shape)) == "halo_stack":
+        return hip_ops().conv_relu_pool_stack_fwd(x, w1, b1, w2, b2, 0, "")
+    h = conv2d_relu_pool(x, w1, b1, 1, 1)
+    return conv2d_relu_pool(h, w2, b2, 1, 1)
+
+
 class _BatchNormFn(torch.autograd.Function):
     """BatchNorm2d (NHWC, batch-stats mode: train AND eval — no running
     buffers; the FedBN-style simplification so the flat parameter vector

@@ -95,6 +95,16 @@ torch::Tensor conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w,
 std::string conv_fwd_pool_impl(std::vector<long> x_shape,
                                std::vector<long> w_shape, long stride,
                                long pad);
+torch::Tensor conv_relu_pool_stack_fwd(torch::Tensor x, torch::Tensor w1,
+                                       torch::Tensor b1, torch::Tensor w2,
+                                       torch::Tensor b2, long max_blocks,
+                                       std::string impl);
+std::string conv_relu_pool_stack_route(std::vector<long> x_shape,
+                                       std::vector<long> w1_shape,
+                                       std::vector<long> w2_shape);
+long halo_stack_group_images_query(std::vector<long> x_shape,
+                                   std::vector<long> w1_shape,
+                                   std::vector<long> w2_shape);
 long halo_conv_group_images_query(std::vector<long> x_shape,
                                   std::vector<long> w_shape, long stride,
                                   long pad);
@@ -273,6 +283,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "images per LDS group of the halo kernel (0: not its geometry)",
         py::arg("x_shape"), py::arg("w_shape"), py::arg("stride"),
         py::arg("pad"));
+  m.def("conv_relu_pool_stack_fwd", &bflc::conv_relu_pool_stack_fwd,
+        "grad-free conv3x3 + ReLU + pool twice (stride 1, pad 1): "
+        "[N, H/4, W/4, Kout2]. impl pins two_call | halo_stack (geometry "
+        "only; '' = conv_relu_pool_stack_route's answer); max_blocks > 0 "
+        "caps the halo kernels' grids",
+        py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("w2"),
+        py::arg("b2"), py::arg("max_blocks") = 0, py::arg("impl") = "");
+  m.def("conv_relu_pool_stack_route", &bflc::conv_relu_pool_stack_route,
+        "what conv_relu_pool_stack_fwd runs: halo_stack | two_call",
+        py::arg("x_shape"), py::arg("w1_shape"), py::arg("w2_shape"));
+  m.def("halo_stack_group_images", &bflc::halo_stack_group_images_query,
+        "images per LDS group of the stack kernel (0: not its geometry)",
+        py::arg("x_shape"), py::arg("w1_shape"), py::arg("w2_shape"));
   m.def("conv2d_relu_pool_route", &bflc::conv2d_relu_pool_route,
         "route conv2d_relu_pool_fwd takes: gemm256_pool | thin_pool | "
         "unfused",

@@ -1190,9 +1190,7 @@ enum class PoolRoute { kUnfused, kGemm256, kThin };
 PoolRoute pool_route(const ConvShape& sh) {
   if (is_1x1_s1(sh)) return PoolRoute::kUnfused;
   if (gemm_conv_fwd_pool_eligible(sh)) return PoolRoute::kGemm256;
-  const long kp = (sh.RSC() + 7) / 8 * 8;
-  if (sh.RSC() <= 16 && gemm_thin_conv_pool_eligible(sh, kp))
-    return PoolRoute::kThin;
+  if (gemm_thin_conv_pool_eligible(sh)) return PoolRoute::kThin;
   return PoolRoute::kUnfused;
 }
 
@@ -1271,9 +1269,7 @@ std::tuple<torch::Tensor, torch::Tensor> relu_pool_fwd_impl(
         route == PoolRoute::kGemm256
             ? gemm_conv_fwd_pool_raw(x, w2, y, sh, &bc, true, ip, halo,
                                      (int)max_blocks)
-            : gemm_thin_conv_pool_raw(
-                  x, pad_w2(w2, (sh.RSC() + 7) / 8 * 8), y, sh, &bc, true,
-                  ip);
+            : gemm_thin_conv_pool_raw(x, w2, y, sh, &bc, true, ip);
     TORCH_CHECK(done, "conv2d_relu_pool: route query and launcher disagree");
     return {y, idx};
   }
@@ -1406,6 +1402,91 @@ long halo_conv_group_images_query(std::vector<long> x_shape,
                                   long pad) {
   return halo_conv_group_images(
       make_shape_dims(x_shape, w_shape, stride, pad));
+}
+
+// ---- the grad-free conv stack: conv3x3 + ReLU + pool, twice ----
+// conv2d_relu_pool_fwd(conv2d_relu_pool_fwd(x, w1, b1, 1, 1), w2, b2, 1,
+// 1). Where the first call would take the thin route and the second the
+// halo kernel, halo_conv_stack_kernel runs both: the first layer's
+// pooled output is computed in LDS by the thin kernel's own chain and
+// never reaches HBM. Same bits as the two calls, which every other shape
+// keeps.
+namespace {
+
+struct StackShapes { ConvShape sh1, sh2; };
+
+StackShapes stack_shapes(const std::vector<long>& xs,
+                         const std::vector<long>& w1s,
+                         const std::vector<long>& w2s) {
+  StackShapes s;
+  s.sh1 = make_shape_dims(xs, w1s, 1, 1);
+  s.sh2 = make_shape_dims({xs[0], s.sh1.OH / 2, s.sh1.OW / 2, w1s[0]}, w2s,
+                          1, 1);
+  return s;
+}
+
+// the stack kernel's chains are those of exactly these two routes
+bool stack_gate(const StackShapes& s) {
+  return pool_route(s.sh1) == PoolRoute::kThin &&
+         pool_route(s.sh2) == PoolRoute::kGemm256 &&
+         halo_stack_gate(s.sh1, s.sh2);
+}
+
+}  // namespace
+
+std::string conv_relu_pool_stack_route(std::vector<long> x_shape,
+                                       std::vector<long> w1_shape,
+                                       std::vector<long> w2_shape) {
+  TORCH_CHECK(w2_shape.size() == 4 && w1_shape.size() == 4 &&
+              w2_shape[3] == w1_shape[0],
+              "conv stack: w2's channels are w1's outputs");
+  return stack_gate(stack_shapes(x_shape, w1_shape, w2_shape))
+             ? "halo_stack"
+             : "two_call";
+}
+
+long halo_stack_group_images_query(std::vector<long> x_shape,
+                                   std::vector<long> w1_shape,
+                                   std::vector<long> w2_shape) {
+  const StackShapes s = stack_shapes(x_shape, w1_shape, w2_shape);
+  return halo_stack_group_images(s.sh1, s.sh2);
+}
+
+// impl: "" = what conv_relu_pool_stack_route reports; "two_call" pins
+// the two calls, "halo_stack" the kernel on its geometry alone (tests,
+// op benchmark). max_blocks > 0 caps the halo kernels' grids.
+torch::Tensor conv_relu_pool_stack_fwd(torch::Tensor x, torch::Tensor w1,
+                                       torch::Tensor b1, torch::Tensor w2,
+                                       torch::Tensor b2, long max_blocks,
+                                       std::string impl) {
+  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(w1); CHECK_CONTIG(w2);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+              w1.scalar_type() == at::kBFloat16 &&
+              w2.scalar_type() == at::kBFloat16 &&
+              b1.scalar_type() == at::kBFloat16 &&
+              b2.scalar_type() == at::kBFloat16, "conv: bf16 only");
+  TORCH_CHECK(impl.empty() || impl == "two_call" || impl == "halo_stack",
+              "conv_relu_pool_stack: impl is '' | two_call | halo_stack");
+  TORCH_CHECK(x.dim() == 4 && w1.dim() == 4 && w2.dim() == 4 &&
+              w2.size(3) == w1.size(0),
+              "conv stack: NHWC x, KRSC weights, w2's channels w1's outputs");
+  const StackShapes s = stack_shapes(x.sizes().vec(), w1.sizes().vec(),
+                                     w2.sizes().vec());
+  const bool pinned = impl == "halo_stack";
+  TORCH_CHECK(!pinned || halo_stack_geometry_ok(s.sh1, s.sh2),
+              "conv_relu_pool_stack: shape outside the stack kernel's "
+              "geometry");
+  if (pinned || (impl.empty() && stack_gate(s))) {
+    auto b1c = b1.contiguous(), b2c = b2.contiguous();
+    auto y = torch::empty({(long)s.sh2.N, (long)s.sh2.OH / 2,
+                           (long)s.sh2.OW / 2, (long)s.sh2.Kout},
+                          x.options());
+    halo_stack_launch(x, w1, b1c, w2, b2c, y, s.sh1, s.sh2, (int)max_blocks);
+    return y;
+  }
+  auto h = std::get<0>(relu_pool_fwd_impl(x, w1, b1, 1, 1, false));
+  return std::get<0>(
+      relu_pool_fwd_impl(h, w2, b2, 1, 1, false, max_blocks, ""));
 }
 
 // Training forward: the same routes, plus the u8 argmax plane the

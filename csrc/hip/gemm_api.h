@@ -116,6 +116,24 @@ void halo_conv_fwd_pool_launch(const torch::Tensor& x,
                                const torch::Tensor& w2, torch::Tensor& y,
                                const ConvShape& sh, const torch::Tensor* bias,
                                bool relu, uint8_t* idx, int max_blocks);
+// The grad-free conv stack as one kernel (halo_conv.hip): sh1 is a thin
+// first layer (3x3, C == 1, Kout == 32, stride 1, pad 1, H and W
+// multiples of 4) on raw [N,H1,W1,1] images, sh2 the halo layer above on
+// its pooled output. Each block computes its sh2 input images in LDS with
+// the thin pooled kernel's per-output chain (thin_pool_chain.h), so y is
+// bitwise gemm_thin_conv_pool_raw then halo_conv_fwd_pool_launch, ReLU on
+// both, while the pooled sh1 activation never reaches HBM.
+bool halo_stack_geometry_ok(const ConvShape& sh1, const ConvShape& sh2);
+// images a block computes per group (0: not eligible)
+int halo_stack_group_images(const ConvShape& sh1, const ConvShape& sh2);
+// geometry && halo_conv_gate(sh2) && BFLC_HALO_STACK; the caller adds
+// that sh1 takes the thin route
+bool halo_stack_gate(const ConvShape& sh1, const ConvShape& sh2);
+void halo_stack_launch(const torch::Tensor& x, const torch::Tensor& w1,
+                       const torch::Tensor& b1, const torch::Tensor& w2,
+                       const torch::Tensor& b2, torch::Tensor& y,
+                       const ConvShape& sh1, const ConvShape& sh2,
+                       int max_blocks);
 // Halo-tile data gradient of that layer's pooled backward
 // (halo_conv.hip): Kout == 64 -> C == 32, 3x3, stride 1, pad 1, even
 // OH/OW. Unpools the pooled (dy, y, idx) into zero-ringed LDS images,
@@ -135,9 +153,11 @@ void halo_pool_dgrad_launch(const torch::Tensor& w,
                             const torch::Tensor& dy_pooled,
                             torch::Tensor* dyf, torch::Tensor& dx,
                             const ConvShape& sh, int max_blocks);
-bool gemm_thin_conv_pool_eligible(const ConvShape& sh, long KT);
+// Thin pooled first layer (3x3, C == 1, stride 1, M >= 65536): w2 is
+// the UNPADDED [Kout, 9] weight view.
+bool gemm_thin_conv_pool_eligible(const ConvShape& sh);
 bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
-                             const torch::Tensor& w2p, torch::Tensor& y,
+                             const torch::Tensor& w2, torch::Tensor& y,
                              const ConvShape& sh, const torch::Tensor* bias,
                              bool relu, uint8_t* idx = nullptr);
 

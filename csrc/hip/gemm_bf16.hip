@@ -43,6 +43,7 @@
 
 #include "common.h"
 #include "gemm_api.h"
+#include "thin_pool_chain.h"
 
 namespace bflc {
 
@@ -1737,20 +1738,22 @@ __global__ __launch_bounds__(256) void gemm_thin_conv_kernel(
 // grad-free forward (3x3, C = 1, stride 1: FEMNIST conv1). One thread
 // per POOLED pixel gathers the 4x4 input patch once (16 taps where the
 // four windows separately read 36), forms the four conv outputs with
-// gemm_thin_conv_kernel's dot — same KT-padded tap order, same packed
-// FMAs, zero taps included — rounds each to bf16 and keeps the pool
-// kernel's running max, so the result is bitwise conv-then-pool while
-// the full-resolution activation never exists. The k loop is outermost
-// so one LDS weight read feeds all four windows.
-template <int KT, bool IDX>
+// gemm_thin_conv_kernel's dot - same tap order, same packed FMAs; that
+// kernel's seven K-padding taps, each fma(+0, +0, acc), are the one
+// `+ 0.f` of thin::conv_pool_chain, the same bits - rounds each to bf16
+// and keeps the pool kernel's running max, so the result is bitwise
+// conv-then-pool while the full-resolution activation never exists. B is
+// the unpadded [N][9] weight view. The chain itself lives in
+// thin_pool_chain.h, shared with the fused conv stack of halo_conv.hip.
+template <bool IDX>
 __global__ __launch_bounds__(256) void gemm_thin_conv_pool_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ B,
     bf16* __restrict__ C, uint8_t* __restrict__ idx,
     const bf16* __restrict__ bias, ConvShape sh, long MP, int N, int relu) {
-  __shared__ float Bl[32 * 64];
-  __shared__ float bl[64];
-  for (int i = threadIdx.x; i < N * KT; i += blockDim.x)
-    Bl[(i % KT) * 64 + i / KT] = b2f(B[i]);
+  __shared__ __align__(32) float Bl[9 * 64];
+  __shared__ __align__(32) float bl[64];
+  for (int i = threadIdx.x; i < N * 9; i += blockDim.x)
+    Bl[(i % 9) * 64 + i / 9] = b2f(B[i]);
   for (int i = threadIdx.x; i < N; i += blockDim.x)
     bl[i] = bias ? b2f(bias[i]) : 0.f;
   __syncthreads();
@@ -1762,7 +1765,7 @@ __global__ __launch_bounds__(256) void gemm_thin_conv_pool_kernel(
     const int rem = (int)(mp % PHW);
     const int ih0 = (rem / PW) * 2 - sh.pad;
     const int iw0 = (rem % PW) * 2 - sh.pad;
-    f32x2v_t pd[4][4];  // input patch, pre-duplicated for v_pk_fma
+    thin::f32x2 pd[4][4];  // input patch, pre-duplicated for v_pk_fma
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int ih = ih0 + r;
@@ -1773,57 +1776,15 @@ __global__ __launch_bounds__(256) void gemm_thin_conv_pool_kernel(
         const bool ok = okh && iw >= 0 && iw < sh.W;
         const float f =
             ok ? b2f(X[((long)n * sh.H + ih) * sh.W + iw]) : 0.f;
-        pd[r][s] = f32x2v_t{f, f};
+        pd[r][s] = thin::f32x2{f, f};
       }
     }
-    const f32x2v_t zero2 = {0.f, 0.f};
     for (int n8 = 0; n8 < N; n8 += 8) {
-      f32x8v_t acc[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        acc[q] = *reinterpret_cast<const f32x8v_t*>(&bl[n8]);
-#pragma unroll
-      for (int k = 0; k < KT; ++k) {
-        const f32x8v_t bv =
-            *reinterpret_cast<const f32x8v_t*>(&Bl[k * 64 + n8]);
-        const f32x2v_t* bv2 = reinterpret_cast<const f32x2v_t*>(&bv);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          // tap k = r*3 + s of window q = (dy, dx); k >= 9 is K padding
-          const f32x2v_t a =
-              k < 9 ? pd[(q >> 1) + k / 3][(q & 1) + k % 3] : zero2;
-          f32x2v_t* acc2 = reinterpret_cast<f32x2v_t*>(&acc[q]);
-#pragma unroll
-          for (int p = 0; p < 4; ++p) acc2[p] += bv2[p] * a;
-        }
-      }
-      float best[8];
-      int bi[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; bi[j] = 0; }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float v = acc[q][j];
-          if (relu && v < 0.f) v = 0.f;
-          const float f = b2f(f2b(v));
-          if (f > best[j]) {
-            best[j] = f;
-            if (IDX) bi[j] = q;
-          }
-        }
-      }
-      bf16x8_t out;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) out[j] = f2b(best[j]);
-      *reinterpret_cast<bf16x8_t*>(&C[mp * N + n8]) = out;
-      if (IDX) {  // training forward: argmax code dy*2 + dx per output
-        u8x8_t oidx;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) oidx[j] = (uint8_t)bi[j];
-        *reinterpret_cast<u8x8_t*>(&idx[mp * N + n8]) = oidx;
-      }
+      thin::bf16x8 out;
+      thin::u8x8 oidx;  // training forward: argmax code dy*2 + dx
+      thin::conv_pool_chain<IDX>(pd, &Bl[n8], 64, &bl[n8], relu, out, oidx);
+      *reinterpret_cast<thin::bf16x8*>(&C[mp * N + n8]) = out;
+      if (IDX) *reinterpret_cast<thin::u8x8*>(&idx[mp * N + n8]) = oidx;
     }
   }
 }
@@ -1986,26 +1947,25 @@ void launch_colsum_final(const float* part, int chunks, long N, bf16* out) {
 // Fused thin conv + ReLU + 2x2 maxpool: true if handled. Same gate as
 // gemm_thin_conv_raw (on the UNPOOLED M, so the two routes switch at
 // the same shape), restricted to the geometry the kernel unrolls.
-bool gemm_thin_conv_pool_eligible(const ConvShape& sh, long KT) {
-  return sh.R == 3 && sh.S == 3 && sh.C == 1 && sh.stride == 1 &&
-         sh.OH % 2 == 0 && sh.OW % 2 == 0 && KT == 16 &&
+bool gemm_thin_conv_pool_eligible(const ConvShape& sh) {
+  return sh.R == 3 && sh.S == 3 && sh.C == 1 && sh.RSC() == 9 &&
+         sh.stride == 1 && sh.OH % 2 == 0 && sh.OW % 2 == 0 &&
          sh.Kout <= 64 && sh.Kout % 8 == 0 && sh.M() >= 65536;
 }
 
 bool gemm_thin_conv_pool_raw(const torch::Tensor& x,
-                             const torch::Tensor& w2p, torch::Tensor& y,
+                             const torch::Tensor& w2, torch::Tensor& y,
                              const ConvShape& sh, const torch::Tensor* bias,
                              bool relu, uint8_t* idx) {
-  const long KT = w2p.size(1);
-  if (!gemm_thin_conv_pool_eligible(sh, KT)) return false;
+  if (!gemm_thin_conv_pool_eligible(sh) || w2.size(1) != 9) return false;
   const long MP = sh.M() / 4;
   const bf16* bs = bias ? (const bf16*)bias->data_ptr() : nullptr;
   const int blocks = (int)std::min<long>((MP + 255) / 256, 16384);
   dispatch_bool(idx != nullptr, [&](auto want_idx) {
     hipLaunchKernelGGL(
-        (gemm_thin_conv_pool_kernel<16, decltype(want_idx)::value>),
+        (gemm_thin_conv_pool_kernel<decltype(want_idx)::value>),
         dim3(blocks), dim3(256), 0, cur_stream(), (const bf16*)x.data_ptr(),
-        (const bf16*)w2p.data_ptr(), (bf16*)y.data_ptr(), idx, bs, sh, MP,
+        (const bf16*)w2.data_ptr(), (bf16*)y.data_ptr(), idx, bs, sh, MP,
         (int)sh.Kout, relu ? 1 : 0);
   });
   HIP_CHECK(hipGetLastError());

@@ -28,10 +28,33 @@
 // bitwise the unsplit gemm256 pooled forward; the gate therefore only
 // takes shapes whose plan has one K slice.
 //
+// The fused grad-free stack (halo_conv_stack_kernel). In committee
+// scoring the layer before is FEMNIST conv1 (3x3, C = 1, Kout = 32, ReLU,
+// 2x2 pool), and one conv2 input image, 12.5 KB, is a pure function of
+// 1.5 KB of raw pixels and 320 parameters. Run as two kernels, conv1
+// writes that tensor to HBM and conv2 reads it straight back: 77 MB of a
+// 101 MB round trip per 3072 images that the result does not need. With
+// STACK the block fetches RAW images (one 16-B granule a thread per
+// group) into small zero-ringed LDS images and COMPUTES the interior of
+// its halo buffers: thin::conv_pool_chain (thin_pool_chain.h), the very
+// helper gemm_thin_conv_pool_kernel calls, eight channels of one pixel
+// per call, stored as one 16-B LDS write. The pooled conv1 activation
+// never reaches HBM, one launch disappears, and the bits are those of the
+// two kernels. conv1 is VALU work (144 packed FMAs an item) next to
+// conv2's MFMA work, so the next group's items run inside this group's
+// tile loop, one 64-item pass per tile - a group has as many of either -
+// rather than as a phase of their own between barriers: two blocks of a
+// CU that run their phases in step would leave the MFMA pipe idle during
+// both stages and the VALU idle during both tile loops. Everything after
+// the stage - B fragments, tile loop, tenth MFMA, POOL epilogue,
+// persistent walk, double buffering - is the same code (STACK is a
+// template parameter of the one body).
+//
 // The second half of the file is the same structure for that layer's
 // data gradient, fed from the pooled tensors (halo_pool_dgrad_kernel).
 #include "common.h"
 #include "gemm_api.h"
+#include "thin_pool_chain.h"
 
 #include <cstdlib>
 
@@ -41,6 +64,7 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 constexpr int kHaloThreads = 256;  // 4 row waves, each all 64 columns
@@ -66,6 +90,26 @@ struct HaloParams {
   Magic m_hw4, m_w, m_phw, m_pw;
 };
 
+// The first layer of the fused stack. Its raw images sit in LDS behind
+// the two halo buffers, each inside a zero ring: pixel (iy, ix) of an
+// image is bf16 element (iy + 1) * rpitch + ix + 4. Four elements of
+// left margin (the ring is the last of them) keep every run of four
+// pixels 8-byte aligned; rpitch = W1 + 8 leaves the right ring and
+// three unused elements.
+struct StackParams {
+  const bf16* w1;  // [32,3,3,1]
+  const bf16* b1;  // [32]
+  int W1;          // raw image width, 2 * W
+  int rpitch;      // ringed raw row, in pixels
+  int rimg;        // ringed raw image, in bytes: (H1 + 2) * rpitch * 2
+  int rgr;         // 16-B granules per raw image: H1 * W1 / 8
+  int raw_off;     // LDS offset of the raw images
+  int w_off;       // LDS offset of the fp32 weights [9][32] + bias [32]
+  Magic m_w1;
+};
+constexpr int kStackKout1 = 32;
+constexpr int kStackWBytes = (9 + 1) * kStackKout1 * 4;
+
 // Row pitch (W+2)*64 + 32: the 16 lanes of one ds_read_b128 group hold
 // both dy rows of four neighbouring windows - 8 pixels of a halo row at
 // 64 B each cover the 16-B slots {0,16,64,80,128,144,192,208} mod 256,
@@ -74,14 +118,17 @@ struct HaloParams {
 // puts kHaloThreads / 256 on each, so two blocks per CU leave a wave
 // 256 VGPRs - the 144 of B, the prefetch and the accumulators fit
 // without scratch.)
-template <int POOLV>
-__launch_bounds__(kHaloThreads, kHaloMinBlocks * (kHaloThreads / 256))
-__global__ void halo_conv_pool_kernel(const unsigned char* __restrict__ x,
-                                      const bf16* __restrict__ w2,
-                                      const bf16* __restrict__ bias,
-                                      bf16* __restrict__ y,
-                                      uint8_t* __restrict__ pool_idx,
-                                      int relu, HaloParams p) {
+//
+// STACK: x is the RAW [N,2H,2W,1] input of the layer before (3x3, C = 1,
+// Kout = 32, stride 1, pad 1, ReLU, 2x2 pool), and the stage computes
+// this layer's input images instead of copying them (header: "The fused
+// grad-free stack"). Everything after the stage is the same code.
+template <int POOLV, bool STACK>
+__device__ __forceinline__ void halo_conv_pool_body(
+    const unsigned char* __restrict__ x, const bf16* __restrict__ w2,
+    const bf16* __restrict__ bias, bf16* __restrict__ y,
+    uint8_t* __restrict__ pool_idx, int relu, const HaloParams& p,
+    const StackParams& sp) {
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr int WR = kHaloThreads / 64 / kHaloWC;  // row waves
   constexpr int FN = 4 / kHaloWC;  // 16-column fragments per wave
@@ -101,10 +148,20 @@ __global__ void halo_conv_pool_kernel(const unsigned char* __restrict__ x,
 
   // zero both buffers once: the ring stays zero for the block's life
   // (staging only ever writes interior pixels)
+  // (STACK: and the raw images behind them, whose ring the first layer's
+  // out-of-image taps read as +0)
   {
     const u32x4_t z = {0u, 0u, 0u, 0u};
-    for (int o = tid * 16; o < 2 * buf_bytes; o += kHaloThreads * 16)
+    const int zbytes = STACK ? sp.w_off : 2 * buf_bytes;
+    for (int o = tid * 16; o < zbytes; o += kHaloThreads * 16)
       *reinterpret_cast<u32x4_t*>(smem + o) = z;
+  }
+  // STACK: the first layer's weights, fp32 and tap-major, and its bias
+  float* w1l = reinterpret_cast<float*>(smem + (STACK ? sp.w_off : 0));
+  if constexpr (STACK) {
+    for (int i = tid; i < kStackKout1 * 9; i += kHaloThreads)
+      w1l[(i % 9) * kStackKout1 + i / 9] = b2f(sp.w1[i]);
+    if (tid < kStackKout1) w1l[9 * kStackKout1 + tid] = b2f(sp.b1[tid]);
   }
 
   // weights: b[t][fn] = w2[col][t*32 + l4*8 ..+7], col = wc*WN + fn*16 + l15
@@ -134,17 +191,92 @@ __global__ void halo_conv_pool_kernel(const unsigned char* __restrict__ x,
                       ch * 16);
   }
   u32x4_t pf[kHaloPF];
+  // STACK: one raw granule (eight pixels) a thread covers a group -
+  // G * H * W * 4 <= kHaloPF * kHaloThreads pixels - and lands in the
+  // ringed raw image as two runs of four (W1 % 4 == 0: a run stays in
+  // its row)
+  int rst[2] = {0, 0};
+  if constexpr (STACK) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const unsigned e = tid * 8 + h * 4;  // pixel of the group
+      const unsigned img = mdiv(e, p.m_hw4);  // H1 * W1 == hw4
+      const unsigned rem = e - img * p.hw4;
+      const unsigned iy = mdiv(rem, sp.m_w1), ix = rem - iy * sp.W1;
+      rst[h] = (int)(sp.raw_off + img * sp.rimg +
+                     ((iy + 1) * sp.rpitch + ix + 4) * 2);
+    }
+  }
+  u32x4_t rpf;
   auto fetch = [&](int g) __attribute__((always_inline)) {
     const int gc = min(p.G, p.N - g * p.G);
-    const int ngr = gc * p.hw4;
-    const unsigned char* src = x + (long)g * p.G * p.hw4 * 16;
+    if constexpr (STACK) {
+      const int ngr = gc * sp.rgr;
+      const unsigned char* src = x + (long)g * p.G * sp.rgr * 16;
+      if (tid < ngr)
+        rpf = *reinterpret_cast<const u32x4_t*>(src + (long)tid * 16);
+      return ngr;
+    } else {
+      const int ngr = gc * p.hw4;
+      const unsigned char* src = x + (long)g * p.G * p.hw4 * 16;
 #pragma unroll
-    for (int i = 0; i < kHaloPF; ++i) {
-      const int gi = tid + i * kHaloThreads;
-      if (gi < ngr)
-        pf[i] = *reinterpret_cast<const u32x4_t*>(src + (long)gi * 16);
+      for (int i = 0; i < kHaloPF; ++i) {
+        const int gi = tid + i * kHaloThreads;
+        if (gi < ngr)
+          pf[i] = *reinterpret_cast<const u32x4_t*>(src + (long)gi * 16);
+      }
+      return ngr;
     }
-    return ngr;
+  };
+  // STACK: a group's raw granules, registers -> the ringed raw images
+  auto raw_put = [&](int ngr) __attribute__((always_inline)) {
+    if (tid < ngr) {
+      *reinterpret_cast<u32x2_t*>(smem + rst[0]) = u32x2_t{rpf.x, rpf.y};
+      *reinterpret_cast<u32x2_t*>(smem + rst[1]) = u32x2_t{rpf.z, rpf.w};
+    }
+  };
+  // STACK: conv1 + bias + ReLU + pool of one item = (channel octet, pixel
+  // of this layer's input) of a group of npix pixels, from the raw
+  // images into halo buffer `buf`. Octet-major, so that a wave reads one
+  // octet's weights (a broadcast) but for three boundaries.
+  auto conv1_item = [&](int buf, int npix, int item)
+      __attribute__((always_inline)) {
+    if (item < 4 * npix) {
+      const int hw = p.hw4 >> 2;
+      const int oct =
+          (item >= npix) + (item >= 2 * npix) + (item >= 3 * npix);
+      const unsigned pix = item - oct * npix;
+      const unsigned img = mdiv(pix * 4, p.m_hw4);
+      const unsigned rem = pix - img * hw;
+      const unsigned py = mdiv(rem, p.m_w), px = rem - py * p.W;
+      // patch rows 2py-1..2py+2, columns 2px-1..2px+2 of the raw image:
+      // ringed elements 2px+3..2px+6, read as three aligned words
+      const unsigned char* rp = smem + sp.raw_off + img * sp.rimg +
+                                ((2 * py) * sp.rpitch + 2 * px + 2) * 2;
+      thin::f32x2 pd[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const unsigned* rw =
+            reinterpret_cast<const unsigned*>(rp + r * sp.rpitch * 2);
+        const unsigned a = rw[0], b = rw[1], c = rw[2];
+        const float f0 = __uint_as_float(a & 0xffff0000u);
+        const float f1 = __uint_as_float(b << 16);
+        const float f2 = __uint_as_float(b & 0xffff0000u);
+        const float f3 = __uint_as_float(c << 16);
+        pd[r][0] = thin::f32x2{f0, f0};
+        pd[r][1] = thin::f32x2{f1, f1};
+        pd[r][2] = thin::f32x2{f2, f2};
+        pd[r][3] = thin::f32x2{f3, f3};
+      }
+      thin::bf16x8 out;
+      thin::u8x8 oidx;
+      thin::conv_pool_chain<false>(pd, w1l + oct * 8, kStackKout1,
+                                   w1l + 9 * kStackKout1 + oct * 8, 1, out,
+                                   oidx);
+      *reinterpret_cast<thin::bf16x8*>(
+          smem + buf * buf_bytes + img * p.img_lds + (py + 1) * p.pitch +
+          (px + 1) * 64 + oct * 16) = out;
+    }
   };
   auto stage = [&](int buf, int ngr) __attribute__((always_inline)) {
 #pragma unroll
@@ -158,10 +290,22 @@ __global__ void halo_conv_pool_kernel(const unsigned char* __restrict__ x,
 
   int g = blockIdx.x;
   if (g >= ngroups) return;  // block-uniform
+  // STACK: the raw granules of the group after this one, in flight from
+  // one iteration's tile loop to the top of the next
+  int ngr_ahead = 0;
   {
     const int ngr = fetch(g);
     __syncthreads();  // zero fill done before the interior lands
-    stage(0, ngr);
+    if constexpr (STACK) {
+      raw_put(ngr);
+      __syncthreads();
+      const int npix = ngr * 2;  // raw pixels / 4: images * H * W
+      for (int item = tid; item < 4 * npix; item += kHaloThreads)
+        conv1_item(0, npix, item);
+      if (g + (int)gridDim.x < ngroups) ngr_ahead = fetch(g + gridDim.x);
+    } else {
+      stage(0, ngr);
+    }
   }
   __syncthreads();
 
@@ -170,7 +314,19 @@ __global__ void halo_conv_pool_kernel(const unsigned char* __restrict__ x,
     const int gnext = g + gridDim.x;
     const bool has_next = gnext < ngroups;  // block-uniform
     int ngr_next = 0;
-    if (has_next) ngr_next = fetch(gnext);
+    if constexpr (STACK) {
+      // the next group's raw images replace this one's, which the
+      // barrier that closed the last iteration left unread; the fetch
+      // two groups ahead takes over the registers
+      ngr_next = ngr_ahead;
+      raw_put(ngr_next);
+      __syncthreads();
+      ngr_ahead = 0;
+      if (gnext + (int)gridDim.x < ngroups)
+        ngr_ahead = fetch(gnext + gridDim.x);
+    } else {
+      if (has_next) ngr_next = fetch(gnext);
+    }
 
     const int gc = min(p.G, p.N - g * p.G);
     const int npp = gc * p.phw;            // pooled pixels of this group
@@ -178,7 +334,21 @@ __global__ void halo_conv_pool_kernel(const unsigned char* __restrict__ x,
     const long pp0 = (long)g * p.G * p.phw;
     const unsigned char* lbuf = smem + cur * buf_bytes;
 
-    for (int mt = wr; mt < ntiles; mt += WR) {
+    // STACK: the next group's conv1 runs inside this group's tile loop,
+    // one 64-item pass of the wave ahead of each of its tiles, so that a
+    // wave alternates VALU and MFMA work a tile at a time and the SIMD's
+    // other wave - the CU's other block - fills the gaps of either kind.
+    // A group has as many passes as tiles (H * W / 16 an image); `npass`
+    // covers a next group that is the larger one all the same.
+    const int npix_next = ngr_next * 2;
+    const int npass = STACK ? (4 * npix_next + 63) >> 6 : 0;
+    const int nloop = STACK ? max(ntiles, npass) : ntiles;
+
+    for (int mt = wr; mt < nloop; mt += WR) {
+      if constexpr (STACK) {
+        if (mt < npass) conv1_item(cur ^ 1, npix_next, mt * 64 + lane);
+        if (mt >= ntiles) continue;
+      }
       // rows are window-major: row = pooled pixel * 4 + dy*2 + dx
       const int pp = mt * 4 + (l15 >> 2);
       const int q = l15 & 3;
@@ -238,10 +408,35 @@ __global__ void halo_conv_pool_kernel(const unsigned char* __restrict__ x,
       }
     }
 
-    if (has_next) stage(cur ^ 1, ngr_next);
+    if constexpr (!STACK) {
+      if (has_next) stage(cur ^ 1, ngr_next);
+    }
     __syncthreads();
     cur ^= 1;
   }
+}
+
+template <int POOLV>
+__launch_bounds__(kHaloThreads, kHaloMinBlocks * (kHaloThreads / 256))
+__global__ void halo_conv_pool_kernel(const unsigned char* __restrict__ x,
+                                      const bf16* __restrict__ w2,
+                                      const bf16* __restrict__ bias,
+                                      bf16* __restrict__ y,
+                                      uint8_t* __restrict__ pool_idx,
+                                      int relu, HaloParams p) {
+  halo_conv_pool_body<POOLV, false>(x, w2, bias, y, pool_idx, relu, p,
+                                    StackParams{});
+}
+
+// The grad-free conv stack: raw pixels in, the second layer's pooled
+// output out, ReLU on both layers, no idx plane.
+__launch_bounds__(kHaloThreads, kHaloMinBlocks * (kHaloThreads / 256))
+__global__ void halo_conv_stack_kernel(const unsigned char* __restrict__ x,
+                                       const bf16* __restrict__ w2,
+                                       const bf16* __restrict__ bias,
+                                       bf16* __restrict__ y, HaloParams p,
+                                       StackParams sp) {
+  halo_conv_pool_body<1, true>(x, w2, bias, y, nullptr, 1, p, sp);
 }
 
 // BFLC_HALO_CONV: 1 (default) routes the gated pooled conv forward to
@@ -276,6 +471,54 @@ HaloGeom halo_geom(const ConvShape& sh) {
   g.img_lds = (int)img;
   g.ok = true;
   return g;
+}
+
+// BFLC_HALO_STACK: 1 (default) lets the gated grad-free conv stack run
+// as halo_conv_stack_kernel, 0 keeps the two calls (A/B runs; same bits).
+bool halo_stack_env_gate() {
+  static const bool v = [] {
+    const char* e = getenv("BFLC_HALO_STACK");
+    return (e ? atoi(e) : 1) != 0;
+  }();
+  return v;
+}
+
+// sh1: the thin first layer on the raw images; sh2: the halo layer on
+// its pooled output. G starts from the halo kernel's (whose staging
+// bound, G * H * W * 4 <= kHaloPF * kHaloThreads, is one raw granule a
+// thread here) and gives way to the raw images and weights in LDS.
+struct StackGeom {
+  bool ok = false;
+  int G = 0, pitch = 0, img_lds = 0;
+  int rpitch = 0, rimg = 0, raw_off = 0, w_off = 0;
+  long lds = 0;
+};
+
+StackGeom stack_geom(const ConvShape& sh1, const ConvShape& sh2) {
+  StackGeom s;
+  if (sh1.C != 1 || sh1.R != 3 || sh1.S != 3 || sh1.stride != 1 ||
+      sh1.pad != 1 || sh1.Kout != kStackKout1 || sh1.N <= 0 ||
+      sh1.H <= 0 || sh1.W <= 0 || sh1.H % 4 != 0 || sh1.W % 4 != 0 ||
+      sh2.N != sh1.N || sh2.H != sh1.H / 2 || sh2.W != sh1.W / 2)
+    return s;
+  const HaloGeom h = halo_geom(sh2);
+  if (!h.ok) return s;
+  s.pitch = h.pitch;
+  s.img_lds = h.img_lds;
+  s.rpitch = sh1.W + 8;
+  s.rimg = (sh1.H + 2) * s.rpitch * 2;
+  for (int G = h.G; G >= 1; --G) {
+    const long raw_off = 2L * G * h.img_lds;
+    const long w_off = (raw_off + (long)G * s.rimg + 63) / 64 * 64;
+    if (w_off + kStackWBytes > kHaloLdsBudget) continue;
+    s.G = G;
+    s.raw_off = (int)raw_off;
+    s.w_off = (int)w_off;
+    s.lds = w_off + kStackWBytes;
+    s.ok = (long)G * sh1.H * sh1.W / 8 <= kHaloThreads;
+    break;
+  }
+  return s;
 }
 
 // ---- data gradient through the pool, fed from the pooled tensors ----
@@ -333,7 +576,6 @@ struct DgradParams {
 };
 
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 
 __device__ __forceinline__ int dg_lds_off(int pix, int slot) {
   return pix * 128 + ((slot ^ ((pix >> 1) & 7)) << 4);
@@ -689,6 +931,72 @@ void halo_conv_fwd_pool_launch(const torch::Tensor& x,
                      (const bf16*)w2.data_ptr(),
                      bias ? (const bf16*)bias->data_ptr() : nullptr,
                      (bf16*)y.data_ptr(), idx, relu ? 1 : 0, p);
+  HIP_CHECK(hipGetLastError());
+}
+
+bool halo_stack_geometry_ok(const ConvShape& sh1, const ConvShape& sh2) {
+  return stack_geom(sh1, sh2).ok;
+}
+
+int halo_stack_group_images(const ConvShape& sh1, const ConvShape& sh2) {
+  return stack_geom(sh1, sh2).G;
+}
+
+// The stack kernel's own part of the gate: its geometry, the halo gate
+// of the second layer (whose chain it issues) and the environment
+// switch. That the first layer would take the thin route, whose chain
+// the stage issues, is the caller's to ask (conv2d.hip).
+bool halo_stack_gate(const ConvShape& sh1, const ConvShape& sh2) {
+  return halo_stack_env_gate() && stack_geom(sh1, sh2).ok &&
+         halo_conv_gate(sh2);
+}
+
+void halo_stack_launch(const torch::Tensor& x, const torch::Tensor& w1,
+                       const torch::Tensor& b1, const torch::Tensor& w2,
+                       const torch::Tensor& b2, torch::Tensor& y,
+                       const ConvShape& sh1, const ConvShape& sh2,
+                       int max_blocks) {
+  const StackGeom g = stack_geom(sh1, sh2);
+  TORCH_CHECK(g.ok, "halo stack: shape outside the kernel's geometry");
+  TORCH_CHECK((long)sh2.N * sh2.H * sh2.W * 64 < (1L << 40), "halo stack: N");
+  TORCH_CHECK(w1.numel() == kStackKout1 * 9 && b1.numel() == kStackKout1 &&
+              w2.numel() == 64 * 9 * 32 && b2.numel() == 64,
+              "halo stack: parameter sizes");
+  HaloParams p;
+  p.N = sh2.N; p.H = sh2.H; p.W = sh2.W;
+  p.PH = sh2.OH / 2; p.PW = sh2.OW / 2;
+  p.G = g.G; p.pitch = g.pitch; p.img_lds = g.img_lds;
+  p.hw4 = sh2.H * sh2.W * 4;
+  p.phw = p.PH * p.PW;
+  p.m_hw4 = make_magic((unsigned)p.hw4);
+  p.m_w = make_magic((unsigned)p.W);
+  p.m_phw = make_magic((unsigned)p.phw);
+  p.m_pw = make_magic((unsigned)p.PW);
+  StackParams sp;
+  sp.w1 = (const bf16*)w1.data_ptr();
+  sp.b1 = (const bf16*)b1.data_ptr();
+  sp.W1 = sh1.W;
+  sp.rpitch = g.rpitch;
+  sp.rimg = g.rimg;
+  sp.rgr = sh1.H * sh1.W / 8;
+  sp.raw_off = g.raw_off;
+  sp.w_off = g.w_off;
+  sp.m_w1 = make_magic((unsigned)sh1.W);
+  const int groups = (sh2.N + g.G - 1) / g.G;
+  int blocks = std::min(groups, kHaloMinBlocks * kNumCU);
+  if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+  static const bool attr_set = [] {
+    HIP_CHECK(hipFuncSetAttribute(
+        (const void*)halo_conv_stack_kernel,
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHaloLdsBudget));
+    return true;
+  }();
+  (void)attr_set;
+  hipLaunchKernelGGL(halo_conv_stack_kernel, dim3((unsigned)blocks),
+                     dim3(kHaloThreads), (size_t)g.lds, cur_stream(),
+                     (const unsigned char*)x.data_ptr(),
+                     (const bf16*)w2.data_ptr(), (const bf16*)b2.data_ptr(),
+                     (bf16*)y.data_ptr(), p, sp);
   HIP_CHECK(hipGetLastError());
 }
 
