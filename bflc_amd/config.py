@@ -18,6 +18,10 @@ from dataclasses import dataclass
 from typing import Any, Dict
 
 
+AGGREGATORS = ("fedavg", "trimmed_mean", "median", "multi_krum")
+MAX_ROBUST_ROWS = 32  # K limit of the robust-aggregation kernels
+
+
 @dataclass
 class FLConfig:
     """Committee-consensus FL protocol + run configuration."""
@@ -62,7 +66,19 @@ class FLConfig:
     # --- sharding ---
     partition: str = "iid"         # iid | dirichlet (non-IID)
     dirichlet_alpha: float = 0.3
-    byzantine_clients: int = 0     # label-flip attackers (BASELINE config 4)
+    byzantine_clients: int = 0     # attackers (BASELINE config 4)
+    byzantine_attack: str = "label_flip"  # label_flip | scale: honest labels,
+                                   # publishes byzantine_scale * delta
+    byzantine_scale: float = -1.0  # scale attack multiplier (-4: boosted flip)
+
+    # --- server-side aggregation rule over the ledger's selection (K
+    # rows; fl/aggregate.py). "fedavg" is the reference's weighted
+    # average; the robust rules need K <= 32. trimmed_mean and median are
+    # unweighted (the ledger's weights are ignored), multi_krum keeps the
+    # ledger's weights on the rows it retains ---
+    aggregator: str = "fedavg"     # fedavg | trimmed_mean | median | multi_krum
+    agg_trim: int = 1              # trimmed_mean: dropped at each end
+    agg_byzantine: int = 1         # multi_krum: assumed bad rows f
 
     # --- execution ---
     use_graphs: bool = True        # hipGraph-captured train step (GPU+SGD;
@@ -96,6 +112,18 @@ class FLConfig:
             raise ValueError(f"unknown lr_schedule {self.lr_schedule!r}")
         if self.lr_schedule == "step" and not self.lr_step_rounds > 0:
             raise ValueError("lr_schedule='step' needs lr_step_rounds > 0")
+        if self.aggregator not in AGGREGATORS:
+            raise ValueError(f"unknown aggregator {self.aggregator!r}")
+        if self.byzantine_attack not in ("label_flip", "scale"):
+            raise ValueError(
+                f"unknown byzantine_attack {self.byzantine_attack!r}")
+        if self.agg_trim < 0 or self.agg_byzantine < 0:
+            raise ValueError("agg_trim and agg_byzantine must be >= 0")
+        if self.aggregator != "fedavg" and \
+                self.aggregate_count > MAX_ROBUST_ROWS:
+            raise ValueError(
+                f"aggregator {self.aggregator!r} needs aggregate_count <= "
+                f"{MAX_ROBUST_ROWS} (the kernels hold K rows in registers)")
         if self.extended_sgd and self.optimizer == "adam":
             raise ValueError(
                 "momentum / weight_decay / prox_mu / clip_norm / lr schedule "

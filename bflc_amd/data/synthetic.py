@@ -19,7 +19,7 @@ import torch
 class Shard:
     x: torch.Tensor          # [n, ...] features
     y: torch.Tensor          # [n] int64 class labels
-    byzantine: bool = False  # label-flip attacker?
+    byzantine: bool = False  # attacker (label-flip or delta-scale)?
 
     @property
     def n(self) -> int:
@@ -117,7 +117,9 @@ def make_federated(cfg, seed_offset: int = 0
 
     Byzantine clients (the last cfg.byzantine_clients) get their labels
     flipped label-flip-attack style: y -> (n_class - 1) - y (BASELINE
-    config 4: committee scoring is the defense).
+    config 4: committee scoring is the defense). With
+    cfg.byzantine_attack == "scale" the labels stay honest and the shards
+    are only marked `byzantine`.
     """
     gen = torch.Generator().manual_seed(cfg.seed + seed_offset)
     total = cfg.samples_per_client * cfg.client_num
@@ -134,7 +136,10 @@ def make_federated(cfg, seed_offset: int = 0
     shards = []
     for i, (sx, sy) in enumerate(parts):
         byz = i >= cfg.client_num - cfg.byzantine_clients
-        if byz:
+        # byzantine_attack == "scale": honest labels; the engine scales
+        # the attacker's published delta instead (model poisoning)
+        if byz and getattr(cfg, "byzantine_attack",
+                           "label_flip") == "label_flip":
             sy = (cfg.n_class - 1) - sy
         shards.append(Shard(sx, sy, byzantine=byz))
     return shards, Shard(x_test, y_test)

@@ -14,7 +14,8 @@ the reference protocol without any polling or sleeps:
   phase V  one all-gather publishes score maps; the comm_count-th feed
            triggers the aggregation decision (.cpp:259-297)
   phase A  every rank applies the identical weighted-FedAvg kernel with
-           a fixed accumulation order and commits (.cpp:349-455)
+           a fixed accumulation order and commits (.cpp:349-455); or,
+           opt-in, a robust rule over the same rows (fl/aggregate.py)
 
 The reference resolves the 16-trainers-race-for-10-slots with
 first-come PBFT ordering; here admission order is the deterministic
@@ -53,6 +54,7 @@ from bflc_amd.chain.identity import (KeyTable, scores_payload,
 from bflc_amd.comm import Transport
 from bflc_amd.config import FLConfig
 from bflc_amd.data.synthetic import Shard
+from bflc_amd.fl.aggregate import aggregate
 from bflc_amd.models import build_model
 from bflc_amd.ops import functional as O
 
@@ -130,6 +132,9 @@ class FLEngine:
         self.ledger.set_global_model(b"")
 
         self._round = 0
+        # info dict of the last round's aggregation (fl/aggregate.py):
+        # rule, effective t or f, and for multi-Krum the origins kept
+        self.last_aggregation: Optional[dict] = None
         self.metrics = JsonlLogger(metrics_path, rank=self.rank)
 
         # which fused local step this engine runs: the legacy
@@ -592,6 +597,14 @@ class FLEngine:
                 delta, n, cost = self._local_train(i)
                 local_updates.append((self.origins[i], delta, n, cost))
                 samples_trained += n * cfg.local_epochs
+        if cfg.byzantine_attack == "scale":
+            # model-poisoning adversary: an attacker trains honestly and
+            # publishes byzantine_scale * delta. Done on the owning rank,
+            # after the client streams joined, for both training paths;
+            # plain torch on purpose (simulation glue, not a hot path)
+            for (o, delta, _, _), i in zip(local_updates, local_subs):
+                if self.shards[i].byzantine:
+                    delta.mul_(float(cfg.byzantine_scale))
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         t1 = time.perf_counter()
@@ -728,23 +741,24 @@ class FLEngine:
         sel = decision.selected
         K = len(sel)
         self.last_decision = decision
+        agg_info = {"aggregator": cfg.aggregator, "rows": 0}
         if K > 0:
             if self._fedavg_buf is None or self._fedavg_buf.shape[0] < K:
                 self._fedavg_buf = torch.empty(
                     K, P, dtype=torch.float32,
                     device=self.global_flat.device)
             deltas = self._fedavg_buf[:K]
-            weights = torch.empty(K, dtype=torch.float32,
-                                  device=self.global_flat.device)
-            for k, (origin, w) in enumerate(sel):
+            for k, (origin, _) in enumerate(sel):
                 deltas[k] = by_origin[origin]
-                weights[k] = float(w)
-            avg = O.weighted_fedavg(deltas, weights)
+            # cfg.aggregator: weighted FedAvg (default) or a robust rule
+            # over the same K rows (fl/aggregate.py)
+            avg, agg_info = aggregate(deltas, sel, cfg)
             # global -= lr * avg  (reference .cpp:403-414)
             O.axpy_(self.global_flat, -cfg.learning_rate, avg)
         # K == 0 (no admitted updates survived): the model is unchanged
         # but the epoch still advances and the committee rotates/refills
         # — the round degrades instead of wedging every replica
+        self.last_aggregation = agg_info
         led.commit_aggregate(b"")
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
@@ -761,7 +775,8 @@ class FLEngine:
             n_selected=K, samples_trained=samples_trained, test_acc=acc)
         self.metrics.log("round", stats,
                          selected=[o for o, _ in decision.selected],
-                         bad_signatures=n_bad_sig, local_lr=local_lr)
+                         bad_signatures=n_bad_sig, local_lr=local_lr,
+                         aggregation=agg_info)
         return stats
 
     # ------------------------------------------------------------------

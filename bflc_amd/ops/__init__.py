@@ -7,7 +7,9 @@ from bflc_amd.ops.functional import (accuracy, accuracy_t, adam_step_,
                                      hip_available, hip_ops, linear,
                                      maxpool2d, relu, sgd_step_,
                                      sgdm_step_, grad_clip_coef_,
-                                     softmax_cross_entropy, weighted_fedavg)
+                                     softmax_cross_entropy, weighted_fedavg,
+                                     order_stat_mean, delta_gram,
+                                     masked_wmean)
 
 __all__ = [
     "functional", "linear", "conv2d", "conv2d_bn", "conv2d_relu_pool",
@@ -15,5 +17,6 @@ __all__ = [
     "add_relu", "maxpool2d", "global_avgpool", "softmax_cross_entropy",
     "accuracy", "accuracy_t", "axpy_", "sgd_step_", "adam_step_",
     "sgdm_step_", "grad_clip_coef_",
-    "weighted_fedavg", "hip_ops", "hip_available",
+    "weighted_fedavg", "order_stat_mean", "delta_gram", "masked_wmean",
+    "hip_ops", "hip_available",
 ]

@@ -873,3 +873,72 @@ def weighted_fedavg(deltas: torch.Tensor, weights: torch.Tensor
     for k in range(deltas.shape[0]):  # fixed order, matches the kernel
         acc += deltas[k].float() * weights[k]
     return acc / weights.sum()
+
+
+# ---------------------------------------------------------------------------
+# robust aggregation (csrc/hip/aggregate.hip): [K, P] fp32 stack, K <= 32
+# ---------------------------------------------------------------------------
+
+MAX_AGG_ROWS = 32
+
+
+def _check_stack(deltas: torch.Tensor) -> None:
+    if deltas.dim() != 2 or deltas.dtype != torch.float32:
+        raise ValueError("deltas must be a [K, P] fp32 tensor")
+    K, P = deltas.shape
+    if not 1 <= K <= MAX_AGG_ROWS or P < 1:
+        raise ValueError(f"need 1 <= K <= {MAX_AGG_ROWS} and P >= 1, got "
+                         f"K={K} P={P}")
+
+
+def order_stat_mean(deltas: torch.Tensor, t: int) -> torch.Tensor:
+    """Per coordinate: sort the K values, drop `t` at each end, add the
+    rest in ascending sorted order in fp32, divide in fp32 by K - 2t.
+    Ordering is by value with every NaN above +inf, so up to t
+    non-finite rows per coordinate are trimmed away and more propagate
+    NaN. t = 0 is the unweighted mean, t = (K-1)//2 the median. Summing
+    in sorted order makes the result bitwise invariant to row order.
+    The CPU path is the oracle of the sort-network kernel."""
+    _check_stack(deltas)
+    K = deltas.shape[0]
+    t = int(t)
+    if t < 0 or 2 * t >= K:
+        raise ValueError(f"need 0 <= 2t < K, got t={t} K={K}")
+    if deltas.is_cuda:
+        return hip_ops().order_stat_mean(deltas, t)
+    srt = torch.sort(deltas, dim=0).values  # NaN sorts last
+    acc = torch.zeros(deltas.shape[1], dtype=torch.float32)
+    for k in range(t, K - t):  # ascending, fp32 adds
+        acc += srt[k]
+    return acc / torch.tensor(float(K - 2 * t), dtype=torch.float32)
+
+
+def delta_gram(deltas: torch.Tensor) -> torch.Tensor:
+    """G[a, b] = sum_i deltas[a, i] * deltas[b, i], fp32 [K, K]. GPU:
+    f32-input MFMA over fixed coordinate ranges, partial tiles added in
+    ascending order (bitwise symmetric, row-permutation equivariant,
+    reproducible). CPU: float64 matmul rounded to fp32."""
+    _check_stack(deltas)
+    if deltas.is_cuda:
+        return hip_ops().delta_gram(deltas)
+    d = deltas.double()
+    return (d @ d.t()).float()
+
+
+def masked_wmean(deltas: torch.Tensor, weights: torch.Tensor
+                 ) -> torch.Tensor:
+    """sum_k w[k] * deltas[k] / sum(w) by fmaf in ascending k — the chain
+    of weighted_fedavg with per-row addressing that is correct for every
+    P. Rows with w[k] == 0 are skipped and never read."""
+    _check_stack(deltas)
+    if weights.shape != (deltas.shape[0],) or \
+            weights.dtype != torch.float32:
+        raise ValueError("weights must be a [K] fp32 tensor")
+    if deltas.is_cuda:
+        return hip_ops().masked_wmean(deltas, weights)
+    acc = torch.zeros(deltas.shape[1], dtype=torch.float32)
+    for k in range(deltas.shape[0]):  # fixed order, matches the kernel
+        if float(weights[k]) == 0.0:
+            continue
+        acc += deltas[k] * weights[k]
+    return acc * (torch.ones((), dtype=torch.float32) / weights.sum())

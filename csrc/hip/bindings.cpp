@@ -42,6 +42,12 @@ void sgdm_master_dev_(torch::Tensor p, c10::optional<torch::Tensor> shadow,
                       torch::Tensor lr_dev, torch::Tensor coef_dev,
                       double momentum, bool nesterov, double wd, double mu);
 
+// aggregate.hip
+torch::Tensor order_stat_mean(torch::Tensor deltas, long t);
+torch::Tensor delta_gram(torch::Tensor deltas);
+std::tuple<long, long> delta_gram_geom_query(long P);
+torch::Tensor masked_wmean(torch::Tensor deltas, torch::Tensor w);
+
 // softmax_ce.hip
 std::tuple<torch::Tensor, torch::Tensor> softmax_ce_fwd(torch::Tensor logits,
                                                         torch::Tensor target);
@@ -210,6 +216,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("p0"), py::arg("lr_dev"), py::arg("coef_dev"),
         py::arg("momentum"), py::arg("nesterov"), py::arg("wd"),
         py::arg("mu"));
+  m.def("order_stat_mean", &bflc::order_stat_mean,
+        "per coordinate: sort the K values (NaN above +inf), drop t at "
+        "each end, ascending fp32 sum / (K - 2t); [K, P] fp32, K <= 32",
+        py::arg("deltas"), py::arg("t"));
+  m.def("delta_gram", &bflc::delta_gram,
+        "G = D D^T of the [K, P] fp32 stack on the f32-input MFMA, "
+        "fixed-order two-stage reduction; K <= 32",
+        py::arg("deltas"));
+  m.def("delta_gram_geom", &bflc::delta_gram_geom_query,
+        "stage-1 geometry of delta_gram at P coordinates: (blocks, "
+        "coordinates per block)",
+        py::arg("P"));
+  m.def("masked_wmean", &bflc::masked_wmean,
+        "sum_k w[k] d[k] / sum(w) by fmaf in ascending k, any P; rows "
+        "with w[k] == 0 are not read",
+        py::arg("deltas"), py::arg("w"));
   m.def("relu_fwd", &bflc::relu_fwd);
   m.def("relu_bwd", &bflc::relu_bwd);
   m.def("relu_bwd_colsum", &bflc::relu_bwd_colsum,
