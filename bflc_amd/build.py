@@ -76,6 +76,7 @@ def _torch_paths() -> tuple[list[str], list[str], list[str]]:
 HIP_SOURCES = [
     "elementwise.hip",
     "optimizer.hip",
+    "privacy.hip",
     "aggregate.hip",
     "softmax_ce.hip",
     "gemm_bf16.hip",

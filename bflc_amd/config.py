@@ -15,7 +15,7 @@ import dataclasses
 import json
 import math
 from dataclasses import dataclass
-from typing import Any, Dict
+from typing import Any, Dict, Optional
 
 
 AGGREGATORS = ("fedavg", "trimmed_mean", "median", "multi_krum")
@@ -80,6 +80,17 @@ class FLConfig:
     agg_trim: int = 1              # trimmed_mean: dropped at each end
     agg_byzantine: int = 1         # multi_krum: assumed bad rows f
 
+    # --- differential privacy of the published update (fl/privacy.py,
+    # DESIGN.md "Round-13"; all defaults mean "off"). The update W0 - W
+    # is clipped to L2 norm dp_clip and Gaussian noise of standard
+    # deviation dp_noise_multiplier * dp_clip is added: by every client
+    # to its own update ("local") or once to the aggregate ("central") ---
+    dp_clip: float = 0.0           # S, model space; the kernels see S / lr
+    dp_noise_multiplier: float = 0.0  # z; needs dp_clip > 0
+    dp_mode: str = "local"         # local | central (central: fedavg only)
+    dp_delta: float = 1e-5         # the delta epsilon is reported for
+    dp_seed: Optional[int] = None  # noise key; None derives it from `seed`
+
     # --- execution ---
     use_graphs: bool = True        # hipGraph-captured train step (GPU+SGD;
                                    # eager fallback elsewhere, fl/graphs.py)
@@ -128,6 +139,21 @@ class FLConfig:
             raise ValueError(
                 "momentum / weight_decay / prox_mu / clip_norm / lr schedule "
                 "fields extend optimizer='sgd' only")
+        for name in ("dp_clip", "dp_noise_multiplier"):
+            if getattr(self, name) < 0:
+                raise ValueError(f"{name} must be >= 0")
+        if self.dp_noise_multiplier > 0 and not self.dp_clip > 0:
+            raise ValueError("dp_noise_multiplier needs dp_clip > 0")
+        if self.dp_mode not in ("local", "central"):
+            raise ValueError(f"unknown dp_mode {self.dp_mode!r}")
+        if self.dp_mode == "central" and self.aggregator != "fedavg":
+            raise ValueError(
+                "dp_mode='central' needs aggregator='fedavg' (the noise is "
+                "calibrated to the weighted mean's sensitivity)")
+        if not 0.0 < self.dp_delta < 1.0:
+            raise ValueError("dp_delta must be in (0, 1)")
+        if self.dp_seed is not None and self.dp_seed < 0:
+            raise ValueError("dp_seed must be >= 0")
 
     # ------------------------------------------------------------------
     _EXTENDED_DEFAULTS = dict(
@@ -141,6 +167,13 @@ class FLConfig:
         default: the local step then runs the sgdm kernels."""
         return any(getattr(self, k) != v
                    for k, v in self._EXTENDED_DEFAULTS.items())
+
+    @property
+    def dp_active(self) -> bool:
+        """True when published updates are clipped (and, with
+        dp_noise_multiplier > 0, noised): the engine then runs the
+        privacy kernels."""
+        return self.dp_clip > 0
 
     def local_lr(self, epoch: int) -> float:
         """Local step size at a ledger epoch (Python doubles; a pure

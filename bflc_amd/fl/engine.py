@@ -54,6 +54,7 @@ from bflc_amd.chain.identity import (KeyTable, scores_payload,
 from bflc_amd.comm import Transport
 from bflc_amd.config import FLConfig
 from bflc_amd.data.synthetic import Shard
+from bflc_amd.fl import privacy
 from bflc_amd.fl.aggregate import aggregate
 from bflc_amd.models import build_model
 from bflc_amd.ops import functional as O
@@ -191,6 +192,14 @@ class FLEngine:
         self._cand_buf: Optional[torch.Tensor] = None
         self._stack_buf: Optional[torch.Tensor] = None
         self._fedavg_buf: Optional[torch.Tensor] = None
+        # differential privacy (cfg.dp_active; fl/privacy.py): per
+        # client a (partials, [coef, sumsq]) pair of device buffers for
+        # the update clip, the coefficients the local clients applied
+        # this round, and the record of the last round (None when off)
+        self._dp_bufs: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._dp_coefs: Dict[str, float] = {}
+        self._dp_one: Optional[torch.Tensor] = None
+        self.last_privacy: Optional[dict] = None
         self._use_graphs = (cfg.use_graphs and self.device.type == "cuda"
                             and os.environ.get("BFLC_GRAPHS", "1") != "0")
         self._concurrent = (self._use_graphs
@@ -319,6 +328,54 @@ class FLEngine:
         self._train_graphs[client] = g
         return g
 
+    def _dp_buffers(self, client: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The client's clip buffers, allocated on first use (on the
+        main stream: the concurrent path asks before it forks)."""
+        if client not in self._dp_bufs:
+            P = self.global_flat.numel()
+            self._dp_bufs[client] = (
+                torch.empty(O.sumsq_partials(P, self.device),
+                            dtype=torch.float32, device=self.device),
+                torch.empty(2, dtype=torch.float32, device=self.device))
+        return self._dp_bufs[client]
+
+    def _publish_delta(self, client: int, out: torch.Tensor,
+                       w: torch.Tensor) -> None:
+        """out = the update client `client` publishes from its trained
+        weights `w`, on the current stream: (W0 - W)/lr (reference
+        main.py:153-154), and with cfg.dp_active clipped to S/lr and, in
+        local mode, noised (fl/privacy.py) — extraction with the sum of
+        squares in the same pass, the clip coefficient on the device,
+        one in-place pass for clip and noise."""
+        cfg = self.cfg
+        if not cfg.dp_active:
+            O.delta_extract_(out, self.global_flat, w, cfg.learning_rate)
+            return
+        part, coef = self._dp_buffers(client)
+        O.delta_extract_sumsq_(out, self.global_flat, w, cfg.learning_rate,
+                               part)
+        O.grad_clip_final_(part, privacy.kernel_clip(cfg), coef)
+        O.dp_privatize_(out, coef, privacy.local_sigma(cfg),
+                        privacy.noise_key(cfg), client, self.ledger.epoch)
+
+    def _extract_update(self, client: int, w: torch.Tensor,
+                        cost: torch.Tensor) -> Tuple[torch.Tensor, float]:
+        """(published delta, summed loss on the host) of the sequential
+        training paths; with cfg.dp_active the one host sync that
+        fetches the loss also fetches the applied clip coefficient."""
+        if not self.cfg.dp_active:
+            host_cost = float(cost)
+            delta = torch.empty_like(self.global_flat)
+            self._publish_delta(client, delta, w)
+            return delta, host_cost
+        delta = torch.empty_like(self.global_flat)
+        self._publish_delta(client, delta, w)
+        host_cost, coef = torch.stack(
+            [cost.detach().float().reshape(()),
+             self._dp_bufs[client][1][0]]).tolist()
+        self._dp_coefs[self.origins[client]] = coef
+        return delta, host_cost
+
     def _local_train(self, client: int) -> Tuple[torch.Tensor, int, float]:
         """Local train step (reference local_training, main.py:103-158):
         start from the global model, run local_epochs passes of
@@ -331,12 +388,9 @@ class FLEngine:
         wg = self._whole_train_graph(client) if self._use_graphs else None
         if wg is not None:
             wg.model.set_flat(self.global_flat)
-            cost = wg.run()
-            avg_cost = float(cost) / wg.n_steps
-            delta = torch.empty_like(self.global_flat)
-            O.delta_extract_(delta, self.global_flat, wg.model.flat.data,
-                             cfg.learning_rate)
-            return delta, n, avg_cost
+            delta, cost = self._extract_update(client, wg.model.flat.data,
+                                               wg.run())
+            return delta, n, cost / wg.n_steps
         bs = min(cfg.batch_size, n)
         total_batches = max(n // bs, 1)
         # capture BEFORE loading the round's weights: graph warmup and
@@ -379,12 +433,9 @@ class FLEngine:
                     else:
                         self.model.sgd_step(cfg.learning_rate)
                     cost_accum += loss.detach()
-        avg_cost = float(cost_accum) / (total_batches * cfg.local_epochs)
-        # delta = (W0 - W)/lr  (reference main.py:153-154)
-        delta = torch.empty_like(self.global_flat)
-        O.delta_extract_(delta, self.global_flat, self.model.flat.data,
-                         cfg.learning_rate)
-        return delta, n, avg_cost
+        delta, cost = self._extract_update(client, self.model.flat.data,
+                                           cost_accum)
+        return delta, n, cost / (total_batches * cfg.local_epochs)
 
     # ------------------------------------------------------------------
     def _pack_candidates(self, updates) -> bool:
@@ -521,6 +572,7 @@ class FLEngine:
         local_lr = cfg.local_lr(epoch)
         if self._lr_dev is not None:
             self._lr_dev.fill_(local_lr)
+        self._dp_coefs.clear()
 
         # ---- phase T: local training on designated submitters ----------
         # Concurrent path: each local trainer's whole-training graph
@@ -554,6 +606,8 @@ class FLEngine:
                 if i not in self._client_delta:
                     self._client_delta[i] = torch.empty_like(
                         self.global_flat)
+                if cfg.dp_active:
+                    self._dp_buffers(i)
             cur = torch.cuda.current_stream()
             costs = {}
             evs = {}
@@ -568,9 +622,8 @@ class FLEngine:
                         evs[i][0].record(s)
                     g.model.set_flat(self.global_flat)
                     costs[i] = g.run()
-                    O.delta_extract_(self._client_delta[i],
-                                     self.global_flat, g.model.flat.data,
-                                     cfg.learning_rate)
+                    self._publish_delta(i, self._client_delta[i],
+                                        g.model.flat.data)
                     if self._phase_debug:
                         evs[i][1].record(s)
             th1 = time.perf_counter()
@@ -585,8 +638,14 @@ class FLEngine:
                       f"| host enqueue {1e3*(th1-th0):.2f} "
                       f"join {1e3*(th2-th1):.2f}", flush=True)
             # ONE host sync for every trainer's accumulated loss
-            costl = torch.stack([costs[i] for i in local_subs]).tolist()
+            fetch = [costs[i] for i in local_subs]
+            if cfg.dp_active:  # the applied clip coefficients ride along
+                fetch += [self._dp_bufs[i][1][0] for i in local_subs]
+            costl = torch.stack(fetch).tolist()
             for j, i in enumerate(local_subs):
+                if cfg.dp_active:
+                    self._dp_coefs[self.origins[i]] = \
+                        costl[len(local_subs) + j]
                 n = self.shards[i].n
                 avg_cost = costl[j] / tgraphs[i].n_steps
                 local_updates.append((self.origins[i],
@@ -742,6 +801,7 @@ class FLEngine:
         K = len(sel)
         self.last_decision = decision
         agg_info = {"aggregator": cfg.aggregator, "rows": 0}
+        central_sigma = 0.0
         if K > 0:
             if self._fedavg_buf is None or self._fedavg_buf.shape[0] < K:
                 self._fedavg_buf = torch.empty(
@@ -753,12 +813,36 @@ class FLEngine:
             # cfg.aggregator: weighted FedAvg (default) or a robust rule
             # over the same K rows (fl/aggregate.py)
             avg, agg_info = aggregate(deltas, sel, cfg)
+            if cfg.dp_active and cfg.dp_mode == "central" \
+                    and cfg.dp_noise_multiplier > 0:
+                # one noise vector on the aggregate, a function of (key,
+                # epoch, coordinate) and the host weights: the same bits
+                # on every replica
+                if self._dp_one is None:
+                    self._dp_one = torch.ones(1, dtype=torch.float32,
+                                              device=self.device)
+                central_sigma = privacy.central_sigma(sel, cfg)
+                O.dp_privatize_(avg, self._dp_one, central_sigma,
+                                privacy.noise_key(cfg), O.DP_CENTRAL_STREAM,
+                                epoch)
             # global -= lr * avg  (reference .cpp:403-414)
             O.axpy_(self.global_flat, -cfg.learning_rate, avg)
         # K == 0 (no admitted updates survived): the model is unchanged
         # but the epoch still advances and the committee rotates/refills
         # — the round degrades instead of wedging every replica
         self.last_aggregation = agg_info
+        extra = {}
+        if cfg.dp_active:
+            # epsilon is a function of the config and the epoch alone
+            # (epoch + 1 rounds done), so checkpoints carry nothing new
+            self.last_privacy = extra["privacy"] = {
+                "mode": cfg.dp_mode, "clip": cfg.dp_clip,
+                "noise_multiplier": cfg.dp_noise_multiplier,
+                "central_sigma": central_sigma,
+                "clip_coef": dict(self._dp_coefs),
+                "delta": cfg.dp_delta,
+                "epsilon": privacy.gaussian_epsilon(
+                    cfg.dp_noise_multiplier, epoch + 1, cfg.dp_delta)}
         led.commit_aggregate(b"")
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
@@ -776,7 +860,7 @@ class FLEngine:
         self.metrics.log("round", stats,
                          selected=[o for o, _ in decision.selected],
                          bad_signatures=n_bad_sig, local_lr=local_lr,
-                         aggregation=agg_info)
+                         aggregation=agg_info, **extra)
         return stats
 
     # ------------------------------------------------------------------

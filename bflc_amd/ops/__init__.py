@@ -9,7 +9,9 @@ from bflc_amd.ops.functional import (accuracy, accuracy_t, adam_step_,
                                      sgdm_step_, grad_clip_coef_,
                                      softmax_cross_entropy, weighted_fedavg,
                                      order_stat_mean, delta_gram,
-                                     masked_wmean)
+                                     masked_wmean, grad_clip_final_,
+                                     delta_extract_sumsq_, dp_privatize_,
+                                     dp_philox_words)
 
 __all__ = [
     "functional", "linear", "conv2d", "conv2d_bn", "conv2d_relu_pool",
@@ -18,5 +20,7 @@ __all__ = [
     "accuracy", "accuracy_t", "axpy_", "sgd_step_", "adam_step_",
     "sgdm_step_", "grad_clip_coef_",
     "weighted_fedavg", "order_stat_mean", "delta_gram", "masked_wmean",
+    "grad_clip_final_", "delta_extract_sumsq_", "dp_privatize_",
+    "dp_philox_words",
     "hip_ops", "hip_available",
 ]

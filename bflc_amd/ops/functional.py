@@ -778,16 +778,163 @@ def grad_clip_coef_(g: torch.Tensor, clip: float,
         hip_ops().grad_clip_coef_(g, float(clip), out)
         return
     with torch.no_grad():
-        ss = g.float().square().sum()
-        if bool(torch.isfinite(ss)):
-            coef = torch.clamp(
-                torch.tensor(float(clip), dtype=torch.float32)
-                / (ss.sqrt() + 1e-6), max=1.0)
+        _clip_coef_cpu(g.float().square().sum(), clip, out)
+
+
+def _clip_coef_cpu(ss: torch.Tensor, clip: float, out: torch.Tensor) -> None:
+    if bool(torch.isfinite(ss)):
+        coef = torch.clamp(
+            torch.tensor(float(clip), dtype=torch.float32)
+            / (ss.sqrt() + 1e-6), max=1.0)
+    else:
+        coef = torch.zeros((), dtype=torch.float32)
+    out[0] = coef
+    if out.numel() > 1:
+        out[1] = ss
+
+
+def grad_clip_final_(part: torch.Tensor, clip: float,
+                     out: torch.Tensor) -> None:
+    """grad_clip_coef_'s second half on per-block partials `part` of a
+    sum of squares (written by delta_extract_sumsq_): out[0] = the clip
+    coefficient, out[1] = the sum. Same kernel, so the same bits as
+    grad_clip_coef_ on the stored vector."""
+    if not clip > 0:
+        raise ValueError("clip must be > 0")
+    if part.is_cuda:
+        hip_ops().grad_clip_final_(part, float(clip), out)
+        return
+    with torch.no_grad():
+        _clip_coef_cpu(part.sum(), clip, out)
+
+
+# ---------------------------------------------------------------------------
+# differential privacy (csrc/hip/privacy.hip; DESIGN.md "Round-13")
+# ---------------------------------------------------------------------------
+
+DP_CENTRAL_STREAM = 0xFFFFFFFF   # noise stream of the aggregate
+_M32 = 0xFFFFFFFF
+
+
+def sumsq_partials(n: int, device) -> int:
+    """Length of the `part` buffer delta_extract_sumsq_ needs for an
+    n-element vector on `device` (the CPU oracle keeps the sum in
+    part[0])."""
+    if torch.device(device).type == "cuda":
+        return grad_sumsq_geom(n)[0]
+    return 1
+
+
+def _philox4x32_10_np(ctr, key0: int, key1: int):
+    """Philox4x32-10 on an [N, 4] array of 32-bit counters, in uint64
+    numpy arithmetic (every product of two 32-bit words fits)."""
+    import numpy as np
+    c = [np.ascontiguousarray(ctr[:, j]).astype(np.uint64) & np.uint64(_M32)
+         for j in range(4)]
+    k0, k1 = int(key0) & _M32, int(key1) & _M32
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    mask, sh = np.uint64(_M32), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]
+        c = [(p1 >> sh) ^ c[1] ^ np.uint64(k0), p1 & mask,
+             (p0 >> sh) ^ c[3] ^ np.uint64(k1), p0 & mask]
+        k0 = (k0 + 0x9E3779B9) & _M32
+        k1 = (k1 + 0xBB67AE85) & _M32
+    return np.stack(c, axis=1)
+
+
+def _dp_normals_np(n: int, seed: int, stream: int, epoch: int):
+    """z(0..n-1) of the noise definition as float64: coordinate i takes
+    element i & 3 of the Box-Muller pairs of Philox block i >> 2."""
+    import numpy as np
+    nb = (n + 3) // 4
+    b = np.arange(nb, dtype=np.uint64)
+    ctr = np.stack([b & np.uint64(_M32), b >> np.uint64(32),
+                    np.full(nb, int(stream) & _M32, dtype=np.uint64),
+                    np.full(nb, int(epoch) & _M32, dtype=np.uint64)], axis=1)
+    seed = int(seed)
+    x = _philox4x32_10_np(ctr, seed & _M32, (seed >> 32) & _M32)
+    u = ((x >> np.uint64(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+    r0 = np.sqrt(-2.0 * np.log(u[:, 0]))
+    r1 = np.sqrt(-2.0 * np.log(u[:, 2]))
+    a0, a1 = 2.0 * np.pi * u[:, 1], 2.0 * np.pi * u[:, 3]
+    z = np.stack([r0 * np.cos(a0), r0 * np.sin(a0),
+                  r1 * np.cos(a1), r1 * np.sin(a1)], axis=1)
+    return z.reshape(-1)[:n]
+
+
+def delta_extract_sumsq_(out: torch.Tensor, global_flat: torch.Tensor,
+                         w: torch.Tensor, lr: float,
+                         part: torch.Tensor) -> None:
+    """delta_extract_ (same bits) and, in the same pass, the per-block
+    partials of sum(out^2) into `part` (sumsq_partials elements), in
+    grad_clip_coef_'s summation order: grad_clip_final_(part, clip, coef)
+    then equals grad_clip_coef_(out, clip, coef) bitwise, one read pass
+    over the vector cheaper. GPU tensors must be 16-byte aligned."""
+    if out.is_cuda:
+        hip_ops().delta_extract_sumsq_(out, global_flat, w, float(lr), part)
+        return
+    delta_extract_(out, global_flat, w, lr)
+    with torch.no_grad():
+        part.zero_()
+        part[0] = out.float().square().sum()
+
+
+def dp_privatize_(d: torch.Tensor, coef_dev: torch.Tensor, sigma: float,
+                  seed: int, stream: int, epoch: int) -> None:
+    """In place on a contiguous fp32 vector: d[i] = fmaf(coef, d[i], n_i)
+    with n_i = fp32(sigma * z(i)) and z the standard normal of
+    (seed, stream, epoch, i) — Philox4x32-10 on counter (i >> 2 lo,
+    i >> 2 hi, stream, epoch) under key (seed lo, seed hi), words to
+    u = ((x >> 8) + 0.5) * 2^-24, Box-Muller, element i & 3. `coef_dev`
+    is a device float (grad_clip_final_'s output). coef == 0 (a
+    non-finite update) publishes n_i alone; sigma == 0 is the clip alone,
+    d[i] = coef * d[i], and runs no generator.
+
+    The CPU oracle evaluates z in float64 and rounds once."""
+    if not sigma >= 0:
+        raise ValueError("sigma must be >= 0")
+    seed, stream, epoch = int(seed), int(stream), int(epoch)
+    if not (0 <= seed < 1 << 64 and 0 <= stream <= _M32
+            and 0 <= epoch <= _M32):
+        raise ValueError("seed is 64-bit, stream and epoch are 32-bit")
+    if d.is_cuda:
+        hip_ops().dp_privatize_(d, coef_dev, float(sigma), seed, stream,
+                                epoch)
+        return
+    import numpy as np
+    if d.dtype != torch.float32 or not d.is_contiguous():
+        raise ValueError("d must be a contiguous fp32 tensor")
+    with torch.no_grad():
+        coef = np.float32(float(coef_dev[0]))
+        sig = np.float32(sigma)
+        dv = d.view(-1).numpy()
+        if sig != 0:
+            z = _dp_normals_np(dv.size, seed, stream, epoch)
+            nz = sig * z.astype(np.float32)
         else:
-            coef = torch.zeros((), dtype=torch.float32)
-        out[0] = coef
-        if out.numel() > 1:
-            out[1] = ss
+            nz = np.zeros(dv.size, dtype=np.float32)
+        if coef == 0:
+            dv[:] = nz
+        elif sig != 0:
+            dv[:] = (np.float64(coef) * dv.astype(np.float64)
+                     + nz.astype(np.float64)).astype(np.float32)
+        else:
+            dv[:] = coef * dv
+
+
+def dp_philox_words(ctr: torch.Tensor, key0: int, key1: int) -> torch.Tensor:
+    """Philox4x32-10 of the [N, 4] int64 counters (each a 32-bit value)
+    under the 32-bit key words: [N, 4] int64 output words. On the GPU
+    this runs the device function dp_privatize_ draws from."""
+    key0, key1 = int(key0), int(key1)
+    if not (0 <= key0 <= _M32 and 0 <= key1 <= _M32):
+        raise ValueError("key words are 32-bit")
+    if ctr.is_cuda:
+        return hip_ops().dp_philox_words(ctr.contiguous(), key0, key1)
+    import numpy as np
+    x = _philox4x32_10_np(ctr.numpy().astype(np.uint64), key0, key1)
+    return torch.from_numpy(x.astype(np.int64))
 
 
 def sgdm_step_(p: torch.Tensor, shadow: Optional[torch.Tensor],

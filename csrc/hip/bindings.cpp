@@ -41,6 +41,15 @@ void sgdm_master_dev_(torch::Tensor p, c10::optional<torch::Tensor> shadow,
                       torch::Tensor g, torch::Tensor buf, torch::Tensor p0,
                       torch::Tensor lr_dev, torch::Tensor coef_dev,
                       double momentum, bool nesterov, double wd, double mu);
+void grad_clip_final_(torch::Tensor part, double clip, torch::Tensor out);
+
+// privacy.hip
+void delta_extract_sumsq_(torch::Tensor out, torch::Tensor global_flat,
+                          torch::Tensor w, double lr, torch::Tensor part);
+void dp_privatize_(torch::Tensor d, torch::Tensor coef_dev, double sigma,
+                   uint64_t seed, uint64_t stream, uint64_t epoch);
+torch::Tensor dp_philox_words(torch::Tensor ctr, uint64_t key0,
+                              uint64_t key1);
 
 // aggregate.hip
 torch::Tensor order_stat_mean(torch::Tensor deltas, long t);
@@ -216,6 +225,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("p0"), py::arg("lr_dev"), py::arg("coef_dev"),
         py::arg("momentum"), py::arg("nesterov"), py::arg("wd"),
         py::arg("mu"));
+  m.def("grad_clip_final_", &bflc::grad_clip_final_,
+        "grad_clip_coef_'s second kernel on per-block partials of a sum "
+        "of squares: out[0] = coef, out[1] = the sum",
+        py::arg("part"), py::arg("clip"), py::arg("out"));
+  m.def("delta_extract_sumsq_", &bflc::delta_extract_sumsq_,
+        "out = (global - w)/lr (delta_extract_'s bits) and, in the same "
+        "pass, part = per-block partials of sum(out^2) in "
+        "grad_clip_coef_'s order; part has grad_sumsq_geom(n)[0] elements",
+        py::arg("out"), py::arg("global_flat"), py::arg("w"), py::arg("lr"),
+        py::arg("part"));
+  m.def("dp_privatize_", &bflc::dp_privatize_,
+        "in place d[i] = fmaf(coef, d[i], sigma * z(i)) with the "
+        "Philox4x32-10 / Box-Muller normal z of (seed, stream, epoch, i); "
+        "coef is a device float, coef == 0 publishes the noise alone, "
+        "sigma == 0 is the clip alone",
+        py::arg("d"), py::arg("coef_dev"), py::arg("sigma"), py::arg("seed"),
+        py::arg("stream"), py::arg("epoch"));
+  m.def("dp_philox_words", &bflc::dp_philox_words,
+        "Philox4x32-10 of the [N, 4] int64 counters under (key0, key1): "
+        "[N, 4] int64 words (test hook of dp_privatize_'s generator)",
+        py::arg("ctr"), py::arg("key0"), py::arg("key1"));
   m.def("order_stat_mean", &bflc::order_stat_mean,
         "per coordinate: sort the K values (NaN above +inf), drop t at "
         "each end, ascending fp32 sum / (K - 2t); [K, P] fp32, K <= 32",
