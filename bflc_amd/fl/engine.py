@@ -2,20 +2,25 @@
 
 One process per GPU; each rank owns a contiguous slice of the FL
 clients and a full replica of the deterministic ledger. A round replays
-the reference protocol without any polling or sleeps:
+the reference protocol without any polling or sleeps,
+one FLEngine method per phase:
 
-  phase T  designated trainers run the local HIP train step
-  phase U  one rank-ordered all-gather publishes (meta, delta) updates;
-           every rank feeds ALL submissions to its ledger replica in the
-           same order => identical admission decisions
-           (reference UploadLocalUpdate guards, .cpp:215-257)
-  phase S  committee clients score every accepted candidate on their own
-           shard (reference local_scoring, main.py:196-217)
-  phase V  one all-gather publishes score maps; the comm_count-th feed
-           triggers the aggregation decision (.cpp:259-297)
-  phase A  every rank applies the identical weighted-FedAvg kernel with
-           a fixed accumulation order and commits (.cpp:349-455); or,
-           opt-in, a robust rule over the same rows (fl/aggregate.py)
+  phase T  (_phase_train) designated trainers run the local HIP train
+           step
+  phase U  (_phase_publish) one rank-ordered all-gather publishes
+           (meta, delta) updates; every rank feeds ALL submissions to
+           its ledger replica in the same order => identical admission
+           decisions (reference UploadLocalUpdate guards, .cpp:215-257)
+  phase S  (_phase_score) committee clients score every accepted
+           candidate on their own shard (reference local_scoring,
+           main.py:196-217)
+  phase V  (_phase_decide) one all-gather publishes score maps; the
+           comm_count-th feed triggers the aggregation decision
+           (.cpp:259-297)
+  phase A  (_phase_aggregate) every rank applies the identical
+           weighted-FedAvg kernel with a fixed accumulation order and
+           commits (.cpp:349-455); or, opt-in, a robust rule over the
+           same rows (fl/aggregate.py)
 
 The reference resolves the 16-trainers-race-for-10-slots with
 first-come PBFT ordering; here admission order is the deterministic
@@ -25,14 +30,14 @@ semantics (rejected updates never influence state), less wasted compute.
 
 Execution model (GPU): each local client's ENTIRE training pass and
 ENTIRE candidate-scoring sweep are captured once as hipGraphs
-(fl/graphs.py) against that client's own model replica and private
-graph pool; within a phase, the participants' replays run CONCURRENTLY
-on slot-indexed HIP streams and join at the phase barrier. Per-client
-kernel order is unchanged, so results are bitwise-identical to the
-sequential path (BFLC_STREAMS=0). The FL-model kernels are
-issue/launch-bound rather than HBM-bound (profiles/r02_pmc_*.md), which
-is why overlap — not more per-kernel bandwidth — is what shortens the
-round.
+(fl/graphs.py, cached by _captured) against that client's own model
+replica and private graph pool; within a phase, the participants'
+replays run CONCURRENTLY on slot-indexed HIP streams and join at the
+phase barrier (_run_on_slot_streams). Per-client kernel order is
+unchanged, so results are bitwise-identical to the sequential path
+(BFLC_STREAMS=0). The FL-model kernels are issue/launch-bound rather
+than HBM-bound (profiles/r02_pmc_*.md), which is why overlap — not more
+per-kernel bandwidth — is what shortens the round.
 
 Data plane (flat fp32 delta tensors, the global model) stays resident on
 the GPU; the ledger's blobs hold b"" markers in engine mode (the
@@ -44,7 +49,7 @@ import os
 import time
 import warnings
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
@@ -54,10 +59,17 @@ from bflc_amd.chain.identity import (KeyTable, scores_payload,
 from bflc_amd.comm import Transport
 from bflc_amd.config import FLConfig
 from bflc_amd.data.synthetic import Shard
-from bflc_amd.fl import privacy
+from bflc_amd.fl import graphs, privacy
 from bflc_amd.fl.aggregate import aggregate
 from bflc_amd.models import build_model
 from bflc_amd.ops import functional as O
+
+# what flows between the phases of a round: an admitted (origin, delta)
+# update — a local one also carries (n_samples, mean loss) — and a
+# scorer's (origin, {candidate origin: accuracy}, HMAC tag)
+Update = Tuple[str, torch.Tensor]
+LocalUpdate = Tuple[str, torch.Tensor, int, float]
+SignedScores = Tuple[str, Dict[str, float], bytes]
 
 
 class StragglerError(RuntimeError):
@@ -150,11 +162,13 @@ class FLEngine:
         # reads it, so a schedule never forces a recapture. The
         # proximal anchor is global_flat itself (address-stable).
         self._lr_dev: Optional[torch.Tensor] = None
-        self._eager_sgdm = None
         if self.local_optimizer == "sgdm":
             self._lr_dev = torch.full(
                 (1,), cfg.local_lr(self.ledger.epoch), dtype=torch.float32,
                 device=self.device)
+        # optimizer of the eager (ungraphed) local step, built on first
+        # use and reset per client pass (graphs.LocalOptimizer)
+        self._eager_opt: Optional[graphs.LocalOptimizer] = None
 
         # hipGraph-captured train step (fl/graphs.py): replay one
         # captured kernel DAG per minibatch instead of relaunching
@@ -169,7 +183,7 @@ class FLEngine:
         self._train_graphs: Dict[int, object] = {}
         self._score_graphs: Dict[int, object] = {}
         self._cand_stack: Optional[torch.Tensor] = None
-        self._graph_pool = None  # shared across all captures (one pool)
+        self._graph_pool = None  # shared by all serialized captures
         # concurrent client streams: the FL-model kernels are
         # issue/launch-bound, not HBM-bound (profiles/r02_pmc_femnist.md)
         # — so a rank hosting several clients overlaps their whole-phase
@@ -211,56 +225,36 @@ class FLEngine:
         """The deterministic prefix of trainers whose updates will be
         admitted (first needed_update_count in (rank, client) order)."""
         roles = self.ledger.roles()
-        order: List[int] = []
-        gathered_order = range(self.cfg.client_num)  # origins are id-sorted
         # global (rank, client-index) order == client index order because
-        # assignment is contiguous ascending
-        for i in gathered_order:
-            role = roles.get(self.origins[i], "trainer")
-            if role == "trainer" or self.cfg.self_scoring:
-                order.append(i)
+        # assignment is contiguous ascending (origins are id-sorted)
+        order = [i for i in range(self.cfg.client_num)
+                 if self.cfg.self_scoring
+                 or roles.get(self.origins[i], "trainer") == "trainer"]
         return order[: self.cfg.needed_update_count]
+
+    def _fence(self) -> None:
+        """Phase boundary: the device is idle when the phase's
+        timestamp is taken."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------
     def _graph_optimizer(self) -> dict:
-        """Optimizer arguments of the graph classes (fl/graphs.py)."""
+        """Optimizer arguments of graphs.LocalOptimizer and of the graph
+        classes that build one (fl/graphs.py)."""
         if self.local_optimizer == "sgdm":
             return dict(optimizer="sgdm", sgdm_cfg=self.cfg,
                         lr_dev=self._lr_dev, p0=self.global_flat)
         return dict(optimizer=self.cfg.optimizer)
 
-    def _sgdm_state(self):
-        """Extended-SGD state of the eager (ungraphed) local step."""
-        if self._eager_sgdm is None:
-            from bflc_amd.models.base import SGDMState
-            self._eager_sgdm = SGDMState.for_model(
-                self.cfg, self.model, self._lr_dev, self.global_flat)
-        return self._eager_sgdm
-
-    # ------------------------------------------------------------------
-    def _graphed_stepper(self, shard: Shard, bs: int):
-        """Lazily capture the train-step hipGraph (fl/graphs.py), one
-        stepper per batch shape (heterogeneous shard sizes each get
-        their own capture instead of silently running eager — round-1
-        ADVICE item). All captures share one graph memory pool. Returns
-        None — and stops trying — if capture is unavailable."""
-        xb, yb = shard.x[:bs], shard.y[:bs]
-        key = (tuple(xb.shape), xb.dtype, tuple(yb.shape))
-        if key in self._steppers:
-            return self._steppers[key]
-        try:
-            from bflc_amd.fl.graphs import GraphedTrainStep
-            st = GraphedTrainStep(self.model, self.cfg.learning_rate, xb,
-                                  yb, pool=self._graph_pool,
-                                  **self._graph_optimizer())
-            if self._graph_pool is None:
-                self._graph_pool = st.pool()
-            self._steppers[key] = st
-        except Exception as e:  # capture unsupported: eager fallback
-            warnings.warn(f"hipGraph capture failed, running eager: {e}")
-            self._use_graphs = False
-            return None
-        return self._steppers[key]
+    def _eager_optimizer(self) -> graphs.LocalOptimizer:
+        """Optimizer of the eager (ungraphed) local step: one per
+        engine, reset at the start of every client pass."""
+        if self._eager_opt is None:
+            self._eager_opt = graphs.LocalOptimizer(
+                self.model, lr=self.cfg.learning_rate, capturable=False,
+                **self._graph_optimizer())
+        return self._eager_opt
 
     # ------------------------------------------------------------------
     def _client_model(self, client: int):
@@ -286,48 +280,144 @@ class FLEngine:
             self._client_streams[slot] = torch.cuda.Stream()
         return self._client_streams[slot]
 
-    def _capture_pool(self, client: int):
-        """Graph memory pool for this client's captures. Concurrent
-        mode: one PRIVATE pool per client (graphs replaying in parallel
-        must not share pool memory); sequential mode: the one shared
-        pool (round-1 ADVICE — serialized replays can share)."""
-        if self._concurrent:
-            return self._client_pools.get(client)
-        return self._graph_pool
+    def _captured(self, cache: dict, key, build: Callable, failure: str,
+                  client: Optional[int] = None,
+                  disable_graphs: bool = False):
+        """The lazily captured graph cache[key]: on first use
+        ``build(model, pool)`` captures it; a capture that raises warns
+        ``failure`` and is remembered as None for this key — or, with
+        ``disable_graphs``, stops the engine trying graphs at all.
 
-    def _note_pool(self, client: int, g) -> None:
-        if self._concurrent:
-            if self._client_pools.get(client) is None:
+        Model and pool: the whole-phase graphs name their ``client`` and
+        in concurrent mode capture against that client's own replica
+        and one PRIVATE pool per client (graphs replaying in parallel
+        must not share weight buffers or pool memory). Everything else
+        — sequential mode, the per-batch stepper, the per-candidate
+        scorer — replays serialized and captures against self.model in
+        the one shared pool (round-1 ADVICE — serialized replays can
+        share). A pool is the pool of its first capture."""
+        if key in cache:
+            return cache[key]
+        private = self._concurrent and client is not None
+        try:
+            if private:
+                model = self._client_model(client)
+                pool = self._client_pools.get(client)
+            else:
+                model, pool = self.model, self._graph_pool
+            g = build(model, pool)
+            if pool is None and private:
                 self._client_pools[client] = g.pool()
-        elif self._graph_pool is None:
-            self._graph_pool = g.pool()
+            elif pool is None:
+                self._graph_pool = g.pool()
+        except Exception as e:
+            warnings.warn(f"{failure}: {e}")
+            if disable_graphs:
+                self._use_graphs = False
+                return None
+            g = None
+        cache[key] = g
+        return g
 
-    # ------------------------------------------------------------------
+    def _graphed_stepper(self, shard: Shard, bs: int):
+        """Lazily capture the train-step hipGraph (fl/graphs.py), one
+        stepper per batch shape (heterogeneous shard sizes each get
+        their own capture instead of silently running eager — round-1
+        ADVICE item). Returns None — and stops trying — if capture is
+        unavailable."""
+        xb, yb = shard.x[:bs], shard.y[:bs]
+        return self._captured(
+            self._steppers, (tuple(xb.shape), xb.dtype, tuple(yb.shape)),
+            lambda model, pool: graphs.GraphedTrainStep(
+                model, self.cfg.learning_rate, xb, yb, pool=pool,
+                **self._graph_optimizer()),
+            "hipGraph capture failed, running eager", disable_graphs=True)
+
     def _whole_train_graph(self, client: int):
         """Per-client whole-local-training graph (shard slices baked in,
         zero per-batch copies); None if capture is unavailable. In
         concurrent mode the graph is captured against the client's own
         model replica (g.model) so replays can overlap."""
-        if client in self._train_graphs:
-            return self._train_graphs[client]
-        try:
-            from bflc_amd.fl.graphs import GraphedLocalTrain
-            shard = self.shards[client]
-            model = (self._client_model(client) if self._concurrent
-                     else self.model)
-            g = GraphedLocalTrain(model, self.cfg.learning_rate,
-                                  shard.x, shard.y, self.cfg.batch_size,
-                                  self.cfg.local_epochs,
-                                  pool=self._capture_pool(client),
-                                  **self._graph_optimizer())
-            self._note_pool(client, g)
-        except Exception as e:
-            warnings.warn(f"whole-train graph capture failed for client "
-                          f"{client}, using per-batch path: {e}")
-            g = None
-        self._train_graphs[client] = g
-        return g
+        return self._captured(
+            self._train_graphs, client,
+            lambda model, pool: graphs.GraphedLocalTrain(
+                model, self.cfg.learning_rate, self.shards[client].x,
+                self.shards[client].y, self.cfg.batch_size,
+                self.cfg.local_epochs, pool=pool,
+                **self._graph_optimizer()),
+            f"whole-train graph capture failed for client {client}, "
+            "using per-batch path", client=client)
 
+    def _phase_scorer(self, scorer: int):
+        """Per-scorer whole-phase scoring graph (all quota candidates in
+        one replay); None if capture is unavailable."""
+        return self._captured(
+            self._score_graphs, scorer,
+            lambda model, pool: graphs.GraphedScorePhase(
+                model, self.shards[scorer].x, self.shards[scorer].y,
+                self._cand_stack, self.global_flat, self.cfg.learning_rate,
+                pool=pool),
+            f"whole-scoring graph capture failed for scorer {scorer}, "
+            "per-candidate path", client=scorer)
+
+    def _graphed_scorer(self, scorer: int):
+        """Per-scorer captured scoring graph (fl/graphs.py); capture
+        mutates the scratch model, which every phase reloads anyway."""
+        return self._captured(
+            self._scorers, scorer,
+            lambda model, pool: graphs.GraphedScore(
+                model, self.shards[scorer].x, self.shards[scorer].y,
+                pool=pool),
+            "score-graph capture failed, running eager")
+
+    # ------------------------------------------------------------------
+    def _run_on_slot_streams(self, label: str, participants: List[int],
+                             enqueue: Callable[[int], torch.Tensor]
+                             ) -> List[torch.Tensor]:
+        """Fork/join of one concurrent phase: ``enqueue(i)`` runs under
+        the stream of participant i's SLOT (its position in the phase,
+        see _client_stream) and returns the device tensor the caller
+        will read back; they come back in participant order. The
+        ordering rules this owns:
+          * every slot stream first waits for the current stream, so
+            whatever the caller allocated or enqueued before the fork
+            (deltas, DP buffers, the lr refill, the packed candidates)
+            is ready — callers allocate BEFORE calling, on the main
+            stream, never inside ``enqueue``;
+          * every slot stream is joined into the current stream before
+            this returns, so the caller's one stacked host read (and
+            the next phase) sees all of them. The host read itself is
+            the caller's.
+        BFLC_PHASE_DEBUG=1 adds per-client device timings (and a device
+        synchronize, so that they can be read)."""
+        cur = torch.cuda.current_stream()
+        out, evs = {}, {}
+        th0 = time.perf_counter()
+        for j, i in enumerate(participants):
+            s = self._client_stream(j)
+            s.wait_stream(cur)
+            with torch.cuda.stream(s):
+                if self._phase_debug:
+                    evs[i] = (torch.cuda.Event(enable_timing=True),
+                              torch.cuda.Event(enable_timing=True))
+                    evs[i][0].record(s)
+                out[i] = enqueue(i)
+                if self._phase_debug:
+                    evs[i][1].record(s)
+        th1 = time.perf_counter()
+        for j in range(len(participants)):
+            cur.wait_stream(self._client_streams[j])
+        if self._phase_debug:
+            torch.cuda.synchronize(self.device)
+            th2 = time.perf_counter()
+            tt = " ".join(f"c{i}:{evs[i][0].elapsed_time(evs[i][1]):.1f}"
+                          for i in participants)
+            print(f"# [debug] epoch {self.ledger.epoch} {label} per-client "
+                  f"ms: {tt} | host enqueue {1e3*(th1-th0):.2f} "
+                  f"join {1e3*(th2-th1):.2f}", flush=True)
+        return [out[i] for i in participants]
+
+    # ------------------------------------------------------------------
     def _dp_buffers(self, client: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """The client's clip buffers, allocated on first use (on the
         main stream: the concurrent path asks before it forks)."""
@@ -358,23 +448,29 @@ class FLEngine:
         O.dp_privatize_(out, coef, privacy.local_sigma(cfg),
                         privacy.noise_key(cfg), client, self.ledger.epoch)
 
+    def _read_losses(self, clients: List[int],
+                     costs: List[torch.Tensor]) -> List[float]:
+        """ONE host sync for the listed clients' summed losses; with
+        cfg.dp_active the clip coefficients they applied ride along
+        (and are kept for the round's privacy record). Every cost is
+        a detached fp32 scalar: a graph's `.cost` or the eager loop's
+        accumulator."""
+        fetch = list(costs)
+        if self.cfg.dp_active:
+            fetch += [self._dp_bufs[i][1][0] for i in clients]
+        host = torch.stack(fetch).tolist()
+        if self.cfg.dp_active:
+            for i, coef in zip(clients, host[len(clients):]):
+                self._dp_coefs[self.origins[i]] = coef
+        return host[:len(clients)]
+
     def _extract_update(self, client: int, w: torch.Tensor,
                         cost: torch.Tensor) -> Tuple[torch.Tensor, float]:
         """(published delta, summed loss on the host) of the sequential
-        training paths; with cfg.dp_active the one host sync that
-        fetches the loss also fetches the applied clip coefficient."""
-        if not self.cfg.dp_active:
-            host_cost = float(cost)
-            delta = torch.empty_like(self.global_flat)
-            self._publish_delta(client, delta, w)
-            return delta, host_cost
+        training paths: publish, then the one host read."""
         delta = torch.empty_like(self.global_flat)
         self._publish_delta(client, delta, w)
-        host_cost, coef = torch.stack(
-            [cost.detach().float().reshape(()),
-             self._dp_bufs[client][1][0]]).tolist()
-        self._dp_coefs[self.origins[client]] = coef
-        return delta, host_cost
+        return delta, self._read_losses([client], [cost])[0]
 
     def _local_train(self, client: int) -> Tuple[torch.Tensor, int, float]:
         """Local train step (reference local_training, main.py:103-158):
@@ -392,53 +488,35 @@ class FLEngine:
                                                wg.run())
             return delta, n, cost / wg.n_steps
         bs = min(cfg.batch_size, n)
-        total_batches = max(n // bs, 1)
+        batches = [(shard.x[bi * bs:(bi + 1) * bs],
+                    shard.y[bi * bs:(bi + 1) * bs])
+                   for bi in range(max(n // bs, 1))] * cfg.local_epochs
         # capture BEFORE loading the round's weights: graph warmup and
         # capture execute real SGD steps and mutate flat/cflat
         stepper = self._graphed_stepper(shard, bs) if self._use_graphs \
             else None
         self.model.set_flat(self.global_flat)
-        if cfg.optimizer == "adam" and stepper is None:
-            m = torch.zeros_like(self.global_flat)
-            v = torch.zeros_like(self.global_flat)
-            step = 0
-        sgdm = None
-        if self.local_optimizer == "sgdm" and stepper is None:
-            sgdm = self._sgdm_state()
-            sgdm.reset()  # fresh momentum per client, as Adam's (m, v)
+        # either way: fresh optimizer state per client pass (Adam's
+        # (m, v, step), sgdm's momentum) and the loss accumulated
+        # on-device — ONE host sync per client per round
         if stepper is not None:
             stepper.cost.zero_()
-            stepper.reset_state()  # fresh Adam (m, v, step) per client
-            for _ in range(cfg.local_epochs):
-                for bi in range(total_batches):
-                    stepper.step(shard.x[bi * bs:(bi + 1) * bs],
-                                 shard.y[bi * bs:(bi + 1) * bs])
+            stepper.reset_state()
+            for xb, yb in batches:
+                stepper.step(xb, yb)
             cost_accum = stepper.cost
         else:
-            # accumulate the loss on-device; ONE host sync per client
-            # per round
+            opt = self._eager_optimizer()
+            opt.reset()
             cost_accum = torch.zeros((), device=self.device)
-            for _ in range(cfg.local_epochs):
-                for bi in range(total_batches):
-                    xb = shard.x[bi * bs:(bi + 1) * bs]
-                    yb = shard.y[bi * bs:(bi + 1) * bs]
-                    self.model.zero_grad()
-                    loss = self.model.loss(xb, yb)
-                    loss.backward()
-                    if cfg.optimizer == "adam":
-                        step += 1
-                        self.model.adam_step(m, v, step, cfg.learning_rate)
-                    elif sgdm is not None:
-                        self.model.sgdm_step(sgdm)
-                    else:
-                        self.model.sgd_step(cfg.learning_rate)
-                    cost_accum += loss.detach()
+            for xb, yb in batches:
+                graphs.train_step(self.model, opt, xb, yb, cost_accum)
         delta, cost = self._extract_update(client, self.model.flat.data,
                                            cost_accum)
-        return delta, n, cost / (total_batches * cfg.local_epochs)
+        return delta, n, cost / len(batches)
 
     # ------------------------------------------------------------------
-    def _pack_candidates(self, updates) -> bool:
+    def _pack_candidates(self, updates: List[Update]) -> bool:
         """Pack the admitted deltas into the persistent [quota, P]
         buffer the whole-scoring graphs bake in; False when the shape
         doesn't fit (degraded round) => per-candidate fallback."""
@@ -454,81 +532,35 @@ class FLEngine:
             self._cand_stack[k].copy_(delta)
         return True
 
-    def _phase_scorer(self, scorer: int):
-        """Per-scorer whole-phase scoring graph (all quota candidates in
-        one replay); None if capture is unavailable."""
-        if scorer in self._score_graphs:
-            return self._score_graphs[scorer]
-        try:
-            from bflc_amd.fl.graphs import GraphedScorePhase
-            shard = self.shards[scorer]
-            model = (self._client_model(scorer) if self._concurrent
-                     else self.model)
-            g = GraphedScorePhase(model, shard.x, shard.y,
-                                  self._cand_stack, self.global_flat,
-                                  self.cfg.learning_rate,
-                                  pool=self._capture_pool(scorer))
-            self._note_pool(scorer, g)
-        except Exception as e:
-            warnings.warn(f"whole-scoring graph capture failed for "
-                          f"scorer {scorer}, per-candidate path: {e}")
-            g = None
-        self._score_graphs[scorer] = g
-        return g
-
-    def _score_candidates(self, scorer: int,
-                          updates: List[Tuple[str, torch.Tensor]],
-                          packed: bool = False) -> Dict[str, float]:
+    def _score_candidates(self, scorer: int, updates: List[Update],
+                          packed: bool = False) -> List[float]:
         """Committee scoring (reference local_scoring, main.py:196-217):
         candidate = W0 - lr*delta, scored by accuracy on the scorer's own
-        local shard."""
+        local shard; one accuracy per update, in their order."""
         if packed:
             g = self._phase_scorer(scorer)
             if g is not None:
-                accs = g.run().tolist()  # one host sync for all K
-                return {origin: accs[k]
-                        for k, (origin, _) in enumerate(updates)}
+                return g.run().tolist()  # one host sync for all K
         shard = self.shards[scorer]
         gs = self._graphed_scorer(scorer) if self._use_graphs else None
         lr = self.cfg.learning_rate
-        accs: List[Tuple[str, torch.Tensor]] = []
+        accs: List[torch.Tensor] = []
         if gs is not None:
-            for origin, delta in updates:
+            for _, delta in updates:
                 # candidate built in the graph's own input buffer — no
                 # per-candidate clone
-                accs.append((origin,
-                             gs.score_candidate(self.global_flat, lr,
-                                                delta)))
+                accs.append(gs.score_candidate(self.global_flat, lr, delta))
         else:
             if self._cand_buf is None:
                 self._cand_buf = torch.empty_like(self.global_flat)
-            for origin, delta in updates:
+            for _, delta in updates:
                 self._cand_buf.copy_(self.global_flat)
                 O.axpy_(self._cand_buf, -lr, delta)
                 self.model.set_flat(self._cand_buf)
                 # device-resident: ONE host sync per scorer (below),
                 # not one per candidate
-                accs.append((origin,
-                             self.model.accuracy_t(shard.x, shard.y)))
-        return {origin: float(a) for origin, a in accs}
-
-    def _graphed_scorer(self, scorer: int):
-        """Per-scorer captured scoring graph (fl/graphs.py); capture
-        mutates the scratch model, which every phase reloads anyway."""
-        if scorer in self._scorers:
-            return self._scorers[scorer]
-        try:
-            from bflc_amd.fl.graphs import GraphedScore
-            shard = self.shards[scorer]
-            gs = GraphedScore(self.model, shard.x, shard.y,
-                              pool=self._graph_pool)
-            if self._graph_pool is None:
-                self._graph_pool = gs.pool()
-            self._scorers[scorer] = gs
-        except Exception as e:
-            warnings.warn(f"score-graph capture failed, running eager: {e}")
-            self._scorers[scorer] = None
-        return self._scorers[scorer]
+                accs.append(self.model.accuracy_t(shard.x, shard.y))
+        return [float(a) for a in accs]
 
     # ------------------------------------------------------------------
     def _gather(self, phase: str, fn, *args):
@@ -558,35 +590,19 @@ class FLEngine:
                 f"{e}{note}") from e
 
     # ------------------------------------------------------------------
-    def run_round(self, eval_global: bool = False) -> RoundStats:
-        cfg, led = self.cfg, self.ledger
-        if led.finished:
-            raise RuntimeError(
-                f"FL run finished: epoch {led.epoch} > max_epoch "
-                f"{cfg.max_epoch} (reference clients exit here, "
-                "main.py:251-252)")
-        epoch = led.epoch
-        t0 = time.perf_counter()
-        # only the LOCAL step size is scheduled; delta extraction,
-        # candidates and the server apply keep cfg.learning_rate
-        local_lr = cfg.local_lr(epoch)
-        if self._lr_dev is not None:
-            self._lr_dev.fill_(local_lr)
-        self._dp_coefs.clear()
+    def _phase_train(self) -> List[LocalUpdate]:
+        """Phase T: local training on the designated submitters that
+        this rank owns.
 
-        # ---- phase T: local training on designated submitters ----------
-        # Concurrent path: each local trainer's whole-training graph
-        # replays on its own HIP stream (its own model replica and
-        # private pool) — set_flat, the replay, and the fused delta
-        # extraction are all enqueued per stream, joined once at the
-        # phase end. Falls back to the sequential loop if any capture is
-        # unavailable.
-        submitters = self._planned_submitters()
-        local_subs = [i for i in submitters if i in self.shards]
-        local_updates: List[Tuple[str, torch.Tensor, int, float]] = []
-        samples_trained = 0
-        conc = self._concurrent and len(local_subs) > 1
-        tgraphs = {}
+        Concurrent path: each local trainer's whole-training graph
+        replays on its own HIP stream (its own model replica and
+        private pool) — set_flat, the replay, and the fused delta
+        extraction are all enqueued per stream, joined once at the
+        phase end. Falls back to the sequential loop if any capture is
+        unavailable."""
+        cfg = self.cfg
+        local_subs = [i for i in self._planned_submitters()
+                      if i in self.shards]
         if self._concurrent and self._round == 0:
             # Pre-capture EVERY local client's training graph now:
             # committee rotation means each client eventually trains,
@@ -594,13 +610,8 @@ class FLEngine:
             # round would put one-time capture cost inside it.
             for i in self.local_clients:
                 self._whole_train_graph(i)
-        if conc:
-            for i in local_subs:
-                g = self._whole_train_graph(i)
-                if g is None:
-                    conc = False
-                    break
-                tgraphs[i] = g
+        conc = self._concurrent and len(local_subs) > 1 and all(
+            self._whole_train_graph(i) is not None for i in local_subs)
         if conc:
             for i in local_subs:  # allocate on the main stream
                 if i not in self._client_delta:
@@ -608,90 +619,65 @@ class FLEngine:
                         self.global_flat)
                 if cfg.dp_active:
                     self._dp_buffers(i)
-            cur = torch.cuda.current_stream()
-            costs = {}
-            evs = {}
-            th0 = time.perf_counter()
-            for j, i in enumerate(local_subs):
-                g, s = tgraphs[i], self._client_stream(j)
-                s.wait_stream(cur)
-                with torch.cuda.stream(s):
-                    if self._phase_debug:
-                        evs[i] = (torch.cuda.Event(enable_timing=True),
-                                  torch.cuda.Event(enable_timing=True))
-                        evs[i][0].record(s)
-                    g.model.set_flat(self.global_flat)
-                    costs[i] = g.run()
-                    self._publish_delta(i, self._client_delta[i],
-                                        g.model.flat.data)
-                    if self._phase_debug:
-                        evs[i][1].record(s)
-            th1 = time.perf_counter()
-            for j in range(len(local_subs)):
-                cur.wait_stream(self._client_streams[j])
-            if self._phase_debug:
-                torch.cuda.synchronize(self.device)
-                th2 = time.perf_counter()
-                tt = " ".join(f"c{i}:{evs[i][0].elapsed_time(evs[i][1]):.1f}"
-                              for i in local_subs)
-                print(f"# [debug] epoch {epoch} train per-client ms: {tt} "
-                      f"| host enqueue {1e3*(th1-th0):.2f} "
-                      f"join {1e3*(th2-th1):.2f}", flush=True)
-            # ONE host sync for every trainer's accumulated loss
-            fetch = [costs[i] for i in local_subs]
-            if cfg.dp_active:  # the applied clip coefficients ride along
-                fetch += [self._dp_bufs[i][1][0] for i in local_subs]
-            costl = torch.stack(fetch).tolist()
-            for j, i in enumerate(local_subs):
-                if cfg.dp_active:
-                    self._dp_coefs[self.origins[i]] = \
-                        costl[len(local_subs) + j]
-                n = self.shards[i].n
-                avg_cost = costl[j] / tgraphs[i].n_steps
-                local_updates.append((self.origins[i],
-                                      self._client_delta[i], n, avg_cost))
-                samples_trained += n * cfg.local_epochs
+
+            def replay(i: int) -> torch.Tensor:
+                g = self._train_graphs[i]
+                g.model.set_flat(self.global_flat)
+                cost = g.run()
+                self._publish_delta(i, self._client_delta[i],
+                                    g.model.flat.data)
+                return cost
+
+            costs = self._read_losses(
+                local_subs,
+                self._run_on_slot_streams("train", local_subs, replay))
+            local_updates = [
+                (self.origins[i], self._client_delta[i], self.shards[i].n,
+                 cost / self._train_graphs[i].n_steps)
+                for i, cost in zip(local_subs, costs)]
         else:
+            local_updates = []
             for i in local_subs:
                 delta, n, cost = self._local_train(i)
                 local_updates.append((self.origins[i], delta, n, cost))
-                samples_trained += n * cfg.local_epochs
         if cfg.byzantine_attack == "scale":
             # model-poisoning adversary: an attacker trains honestly and
             # publishes byzantine_scale * delta. Done on the owning rank,
             # after the client streams joined, for both training paths;
             # plain torch on purpose (simulation glue, not a hot path)
-            for (o, delta, _, _), i in zip(local_updates, local_subs):
+            for (_, delta, _, _), i in zip(local_updates, local_subs):
                 if self.shards[i].byzantine:
                     delta.mul_(float(cfg.byzantine_scale))
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        t1 = time.perf_counter()
+        return local_updates
 
-        # ---- phase U: publish updates (one RCCL all-gather) -------------
-        # each submission carries an HMAC tag binding (origin, epoch,
-        # meta) to the origin's bootstrap key (chain/identity.py); every
-        # replica verifies before feeding its ledger, so a forged origin
-        # is rejected deterministically on all ranks (reference: one
-        # ECDSA key per client, get_batch_accounts.sh)
+    def _phase_publish(self, epoch: int, local_updates: List[LocalUpdate]
+                       ) -> Tuple[List[Update], int]:
+        """Phase U: publish updates (one RCCL all-gather). Returns the
+        admitted updates and the number of bad signatures.
+
+        Each submission carries an HMAC tag binding (origin, epoch,
+        meta) to the origin's bootstrap key (chain/identity.py); every
+        replica verifies before feeding its ledger, so a forged origin
+        is rejected deterministically on all ranks (reference: one
+        ECDSA key per client, get_batch_accounts.sh)."""
         metas = [(o, epoch, n, c,
                   self.keys.sign("update", o, epoch, update_payload(n, c)))
                  for (o, delta, n, c) in local_updates]
         all_metas = self._gather("updates", self.t.all_gather_objects, metas)
         max_subs = max((len(m) for m in all_metas), default=0)
-        P = self.global_flat.numel()
         rows = max(max_subs, 1)
         # cached, never zeroed: rows beyond a rank's own submission count
         # are never read back (unpack walks rank_metas, not the padding)
         if self._stack_buf is None or self._stack_buf.shape[0] < rows:
-            self._stack_buf = torch.empty(rows, P, dtype=torch.float32,
-                                          device=self.global_flat.device)
+            self._stack_buf = torch.empty(
+                rows, self.global_flat.numel(), dtype=torch.float32,
+                device=self.global_flat.device)
         stack = self._stack_buf[:rows]
         for j, (_, delta, _, _) in enumerate(local_updates):
             stack[j] = delta
         gathered = self._gather("update-deltas", self.t.all_gather_tensor,
                                 stack)
-        updates: List[Tuple[str, torch.Tensor]] = []
+        updates: List[Update] = []
         n_bad_sig = 0
         for r, rank_metas in enumerate(all_metas):
             for j, (origin, ep, n, c, tag) in enumerate(rank_metas):
@@ -699,103 +685,78 @@ class FLEngine:
                                         update_payload(n, c), tag):
                     n_bad_sig += 1
                     continue
-                code = led.upload_local_update(origin, b"", ep, n, c)
+                code = self.ledger.upload_local_update(origin, b"", ep, n, c)
                 if code == Admit.ACCEPTED:
                     updates.append((origin, gathered[r][j].to(self.device)))
-        t2 = time.perf_counter()
+        return updates, n_bad_sig
 
-        # ---- phase S: committee scoring ---------------------------------
-        roles = led.roles()
-        if cfg.self_scoring:
+    def _phase_score(self, epoch: int, updates: List[Update]
+                     ) -> List[SignedScores]:
+        """Phase S: committee scoring; the signed score map of every
+        local scorer.
+
+        Concurrent path: every local scorer's whole-scoring graph (all
+        K candidates in one replay) runs on its own slot stream; scores
+        are read back once after the join."""
+        roles = self.ledger.roles()
+        if self.cfg.self_scoring:
             local_scorers = list(self.shards.keys())
         else:
             local_scorers = [i for i in self.local_clients
                              if roles.get(self.origins[i]) == "comm"]
         packed = bool(local_scorers) and self._pack_candidates(updates)
-        my_scores = []
         if self._concurrent and packed and self._round == 0:
             # pre-capture every local client's scoring graph (rotation:
             # each client eventually sits on the committee) so later
             # rounds never pay capture cost
             for i in self.local_clients:
                 self._phase_scorer(i)
-        # Concurrent path: every local scorer's whole-scoring graph (all
-        # K candidates in one replay) runs on its own slot stream;
-        # scores are read back once after the join.
-        conc_s = self._concurrent and packed and len(local_scorers) > 1
-        sgraphs = {}
-        if conc_s:
-            for i in local_scorers:
-                g = self._phase_scorer(i)
-                if g is None:
-                    conc_s = False
-                    break
-                sgraphs[i] = g
-        if conc_s:
-            cur = torch.cuda.current_stream()
-            res = {}
-            evs = {}
-            th0 = time.perf_counter()
-            for j, i in enumerate(local_scorers):
-                s = self._client_stream(j)
-                s.wait_stream(cur)
-                with torch.cuda.stream(s):
-                    if self._phase_debug:
-                        evs[i] = (torch.cuda.Event(enable_timing=True),
-                                  torch.cuda.Event(enable_timing=True))
-                        evs[i][0].record(s)
-                    res[i] = sgraphs[i].run_inplace()
-                    if self._phase_debug:
-                        evs[i][1].record(s)
-            th1 = time.perf_counter()
-            for j in range(len(local_scorers)):
-                cur.wait_stream(self._client_streams[j])
-            if self._phase_debug:
-                torch.cuda.synchronize(self.device)
-                th2 = time.perf_counter()
-                tt = " ".join(f"c{i}:{evs[i][0].elapsed_time(evs[i][1]):.1f}"
-                              for i in local_scorers)
-                print(f"# [debug] epoch {epoch} score per-client ms: {tt} "
-                      f"| host enqueue {1e3*(th1-th0):.2f} "
-                      f"join {1e3*(th2-th1):.2f}", flush=True)
+        conc = self._concurrent and packed and len(local_scorers) > 1 \
+            and all(self._phase_scorer(i) is not None for i in local_scorers)
+        if conc:
             # ONE host sync for all scorers' [K] accuracy vectors
-            alla = torch.stack([res[i] for i in local_scorers]).tolist()
-            for j, i in enumerate(local_scorers):
-                accs = alla[j]
-                smap = {origin: accs[k]
-                        for k, (origin, _) in enumerate(updates)}
-                o = self.origins[i]
-                my_scores.append((o, smap, self.keys.sign(
-                    "scores", o, epoch, scores_payload(smap))))
+            all_accs = torch.stack(self._run_on_slot_streams(
+                "score", local_scorers,
+                lambda i: self._score_graphs[i].run_inplace())).tolist()
         else:
-            for i in local_scorers:
-                o = self.origins[i]
-                smap = self._score_candidates(i, updates, packed=packed)
-                my_scores.append((o, smap, self.keys.sign(
-                    "scores", o, epoch, scores_payload(smap))))
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        t3 = time.perf_counter()
+            all_accs = [self._score_candidates(i, updates, packed=packed)
+                        for i in local_scorers]
+        my_scores = []
+        for i, accs in zip(local_scorers, all_accs):
+            o = self.origins[i]
+            smap = {origin: acc for (origin, _), acc in zip(updates, accs)}
+            my_scores.append((o, smap, self.keys.sign(
+                "scores", o, epoch, scores_payload(smap))))
+        return my_scores
 
-        # ---- phase V: publish scores, decide ----------------------------
+    def _phase_decide(self, epoch: int, my_scores: List[SignedScores]):
+        """Phase V: publish scores, decide. Returns the ledger's
+        aggregation decision and the number of bad signatures."""
         all_scores = self._gather("scores", self.t.all_gather_objects,
                                   my_scores)
         decision = None
+        n_bad_sig = 0
         for rank_scores in all_scores:
             for origin, smap, tag in rank_scores:
                 if not self.keys.verify("scores", origin, epoch,
                                         scores_payload(smap), tag):
                     n_bad_sig += 1
                     continue
-                d = led.upload_scores(origin, epoch, smap)
+                d = self.ledger.upload_scores(origin, epoch, smap)
                 if d is not None:
                     decision = d
         if decision is None:
             raise RuntimeError(
                 f"round {epoch}: no aggregation decision "
-                f"(scores={led.score_count}/{cfg.comm_count})")
+                f"(scores={self.ledger.score_count}/{self.cfg.comm_count})")
+        return decision, n_bad_sig
 
-        # ---- phase A: weighted FedAvg + commit --------------------------
+    def _phase_aggregate(self, epoch: int, updates: List[Update],
+                         decision) -> Tuple[dict, dict]:
+        """Phase A: weighted FedAvg (or a robust rule) + commit. Returns
+        the aggregation info and the extra fields of the round's metrics
+        record."""
+        cfg = self.cfg
         by_origin = dict(updates)
         sel = decision.selected
         K = len(sel)
@@ -805,7 +766,7 @@ class FLEngine:
         if K > 0:
             if self._fedavg_buf is None or self._fedavg_buf.shape[0] < K:
                 self._fedavg_buf = torch.empty(
-                    K, P, dtype=torch.float32,
+                    K, self.global_flat.numel(), dtype=torch.float32,
                     device=self.global_flat.device)
             deltas = self._fedavg_buf[:K]
             for k, (origin, _) in enumerate(sel):
@@ -843,9 +804,36 @@ class FLEngine:
                 "delta": cfg.dp_delta,
                 "epsilon": privacy.gaussian_epsilon(
                     cfg.dp_noise_multiplier, epoch + 1, cfg.dp_delta)}
-        led.commit_aggregate(b"")
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
+        self.ledger.commit_aggregate(b"")
+        return agg_info, extra
+
+    def run_round(self, eval_global: bool = False) -> RoundStats:
+        cfg, led = self.cfg, self.ledger
+        if led.finished:
+            raise RuntimeError(
+                f"FL run finished: epoch {led.epoch} > max_epoch "
+                f"{cfg.max_epoch} (reference clients exit here, "
+                "main.py:251-252)")
+        epoch = led.epoch
+        t0 = time.perf_counter()
+        # only the LOCAL step size is scheduled; delta extraction,
+        # candidates and the server apply keep cfg.learning_rate
+        local_lr = cfg.local_lr(epoch)
+        if self._lr_dev is not None:
+            self._lr_dev.fill_(local_lr)
+        self._dp_coefs.clear()
+
+        local_updates = self._phase_train()
+        self._fence()
+        t1 = time.perf_counter()
+        updates, bad_update_sigs = self._phase_publish(epoch, local_updates)
+        t2 = time.perf_counter()
+        my_scores = self._phase_score(epoch, updates)
+        self._fence()
+        t3 = time.perf_counter()
+        decision, bad_score_sigs = self._phase_decide(epoch, my_scores)
+        agg_info, extra = self._phase_aggregate(epoch, updates, decision)
+        self._fence()
         t4 = time.perf_counter()
 
         acc = None
@@ -856,11 +844,13 @@ class FLEngine:
             epoch=epoch, wall_s=t4 - t0, train_s=t1 - t0, gather_s=t2 - t1,
             score_s=t3 - t2, aggregate_s=t4 - t3,
             global_loss=led.global_loss, n_updates=len(updates),
-            n_selected=K, samples_trained=samples_trained, test_acc=acc)
+            n_selected=len(decision.selected),
+            samples_trained=sum(n for _, _, n, _ in local_updates)
+            * cfg.local_epochs, test_acc=acc)
         self.metrics.log("round", stats,
                          selected=[o for o, _ in decision.selected],
-                         bad_signatures=n_bad_sig, local_lr=local_lr,
-                         aggregation=agg_info, **extra)
+                         bad_signatures=bad_update_sigs + bad_score_sigs,
+                         local_lr=local_lr, aggregation=agg_info, **extra)
         return stats
 
     # ------------------------------------------------------------------

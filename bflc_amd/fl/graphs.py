@@ -38,31 +38,123 @@ The extended SGD step (``optimizer="sgdm"``: momentum, weight decay,
 FedProx, clipping, scheduled lr) captures the same way: its learning
 rate and clip coefficient are DEVICE floats (csrc/hip/optimizer.hip), so
 the caller refills ``lr_dev`` between replays and the same graph runs at
-the new step size. The graph classes own the momentum buffer and the
-coefficient; ``lr_dev`` and the proximal anchor ``p0`` are the caller's
-and must keep their addresses.
+the new step size. The optimizer object owns the momentum buffer and
+the coefficient; ``lr_dev`` and the proximal anchor ``p0`` are the
+caller's and must keep their addresses.
+
+The optimizer kind is dispatched, and its per-pass state allocated and
+reset, in ONE place: ``LocalOptimizer``. Both train graphs hold a
+capturable one; the engine's eager loop holds a non-capturable one.
 
 Capture executes real kernels, so construction MUTATES the weights —
 callers build the stepper before loading the round's global weights
 (engine.py does this), or snapshot/restore around construction.
 
-All captures in one engine share ONE graph memory pool (pass
-``pool=graph.pool()`` of the first capture): per-scorer private pools
-each held full-shard forward activations and grew GPU memory with the
-number of local scorers (round-1 ADVICE item).
+Graph memory pools are the caller's choice (``pool=`` of every class,
+``graph.pool()`` of an earlier capture). Graphs that only ever replay
+one after another share ONE pool — per-scorer private pools each held
+full-shard forward activations and grew GPU memory with the number of
+local scorers (round-1 ADVICE item) — which is what the engine does for
+the per-batch stepper, the per-candidate scorer and everything in
+sequential mode. Graphs that replay CONCURRENTLY must not share pool
+memory: in concurrent mode the engine gives each local client's
+whole-phase graphs one private pool per client.
 """
 from __future__ import annotations
 
 import torch
 
 
-def _sgdm_state(model, sgdm_cfg, lr_dev, p0):
-    """Graph-owned extended-SGD state: fresh buf + coef_dev, the
-    caller's lr_dev / p0 (fixed addresses, baked into the capture)."""
-    from bflc_amd.models.base import SGDMState
-    if sgdm_cfg is None or lr_dev is None:
-        raise ValueError("optimizer='sgdm' needs sgdm_cfg and lr_dev")
-    return SGDMState.for_model(sgdm_cfg, model, lr_dev, p0)
+class LocalOptimizer:
+    """The local step's optimizer: per-pass state, ``step()`` and
+    ``reset()`` for ``sgd | sgdm | adam``. ``capturable`` picks the
+    Adam form: the device-step kernel pair (hipGraph-safe) or the eager
+    kernel with a host step counter — two kernels on purpose, they
+    differ in where 1 - beta^t is computed. sgdm owns a fresh buf +
+    coef_dev and uses the caller's lr_dev / p0 (fixed addresses, baked
+    into a capture)."""
+
+    def __init__(self, model, optimizer: str, lr: float, capturable: bool,
+                 sgdm_cfg=None, lr_dev=None, p0=None) -> None:
+        self.model = model
+        self.kind = optimizer
+        self.capturable = capturable
+        self.lr = float(lr)
+        if optimizer == "adam":
+            if capturable and model.cflat is model.flat:
+                raise RuntimeError(
+                    "graphed Adam needs the bf16-shadow model (the "
+                    "device-step kernel is adam_master_graph_)")
+            self.m = torch.zeros_like(model.flat)
+            self.v = torch.zeros_like(model.flat)
+            self.step_n = 0  # host step counter of the eager form
+            if capturable:
+                self.step_t = torch.zeros(1, device=model.device,
+                                          dtype=torch.int32)
+                self.bc = torch.zeros(2, device=model.device,
+                                      dtype=torch.float32)
+        elif optimizer == "sgdm":
+            from bflc_amd.models.base import SGDMState
+            if sgdm_cfg is None or lr_dev is None:
+                raise ValueError("optimizer='sgdm' needs sgdm_cfg and lr_dev")
+            self.sgdm = SGDMState.for_model(sgdm_cfg, model, lr_dev, p0)
+        elif optimizer != "sgd":
+            raise ValueError(optimizer)
+
+    def step(self) -> None:
+        if self.kind == "sgd":
+            self.model.sgd_step(self.lr)
+        elif self.kind == "sgdm":
+            self.model.sgdm_step(self.sgdm)
+        elif self.capturable:
+            self.model.adam_step_graph(self.m, self.v, self.step_t,
+                                       self.bc, self.lr)
+        else:
+            self.step_n += 1
+            self.model.adam_step(self.m, self.v, self.step_n, self.lr)
+
+    def reset(self) -> None:
+        """Fresh state for a new client pass, on the current stream
+        (the reference builds a new optimizer per round, main.py:109)."""
+        if self.kind == "adam":
+            self.m.zero_()
+            self.v.zero_()
+            self.step_n = 0
+            if self.capturable:
+                self.step_t.zero_()
+        elif self.kind == "sgdm":
+            self.sgdm.reset()
+
+
+def train_step(model, opt: LocalOptimizer, xb, yb, cost=None):
+    """One local minibatch step, in the order every path keeps:
+    zero_grad, loss, backward, optimizer step, then (only when
+    accumulating) cost += loss."""
+    model.zero_grad()
+    loss = model.loss(xb, yb)
+    loss.backward()
+    opt.step()
+    if cost is not None:
+        cost.add_(loss.detach().float())
+
+
+def _capture(warm, body, pool, zero_grad_of=None):
+    """Run ``warm()`` on a side stream (materializes autograd engine
+    state and cat/workspace allocations so none of it happens
+    mid-capture), join, then capture ``body()`` into a new graph."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        warm()
+    torch.cuda.current_stream().wait_stream(side)
+    if zero_grad_of is not None:
+        # grads=None at capture: backward's grad tensors are allocated
+        # from the graph pool and rewritten in place on every replay
+        zero_grad_of.zero_grad()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, pool=pool):
+        body()
+    return graph
 
 
 class GraphedTrainStep:
@@ -81,66 +173,22 @@ class GraphedTrainStep:
                                 dtype=torch.float32)
         self.sx.copy_(x_proto)
         self.sy.copy_(y_proto)
-        if optimizer == "adam":
-            if model.cflat is model.flat:
-                raise RuntimeError(
-                    "graphed Adam needs the bf16-shadow model (the "
-                    "device-step kernel is adam_master_graph_)")
-            self.m = torch.zeros_like(model.flat)
-            self.v = torch.zeros_like(model.flat)
-            self.step_t = torch.zeros(1, device=model.device,
-                                      dtype=torch.int32)
-            self.bc = torch.zeros(2, device=model.device,
-                                  dtype=torch.float32)
-        elif optimizer == "sgdm":
-            self.sgdm = _sgdm_state(model, sgdm_cfg, lr_dev, p0)
-        elif optimizer != "sgd":
-            raise ValueError(optimizer)
-        self._lr = float(lr)
+        self.opt = LocalOptimizer(model, optimizer, lr, True, sgdm_cfg,
+                                  lr_dev, p0)
 
-        # warmup on a side stream (materializes autograd engine state,
-        # cat/workspace allocations) so none of it happens mid-capture
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        def warm():
             for _ in range(max(warmup, 1)):
-                self._one_step()
-        torch.cuda.current_stream().wait_stream(side)
+                train_step(model, self.opt, self.sx, self.sy)
 
-        # grads=None at capture: backward's grad tensors are allocated
-        # from the graph pool and rewritten in place on every replay
-        self.model.zero_grad()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, pool=pool):
-            loss = self.model.loss(self.sx, self.sy)
-            loss.backward()
-            self._optim_step()
-            self.cost.add_(loss.detach().float())
-
-    def _optim_step(self) -> None:
-        if self.optimizer == "adam":
-            self.model.adam_step_graph(self.m, self.v, self.step_t,
-                                       self.bc, self._lr)
-        elif self.optimizer == "sgdm":
-            self.model.sgdm_step(self.sgdm)
-        else:
-            self.model.sgd_step(self._lr)
-
-    def _one_step(self) -> None:
-        self.model.zero_grad()
-        loss = self.model.loss(self.sx, self.sy)
-        loss.backward()
-        self._optim_step()
+        self.graph = _capture(
+            warm, lambda: train_step(model, self.opt, self.sx, self.sy,
+                                     self.cost),
+            pool, zero_grad_of=model)
 
     def reset_state(self) -> None:
         """Fresh optimizer for a new client/round (reference builds a
         new TF graph per round, main.py:109)."""
-        if self.optimizer == "adam":
-            self.m.zero_()
-            self.v.zero_()
-            self.step_t.zero_()
-        elif self.optimizer == "sgdm":
-            self.sgdm.reset()
+        self.opt.reset()
 
     def pool(self):
         return self.graph.pool()
@@ -177,52 +225,21 @@ class GraphedLocalTrain:
         bs = min(batch_size, n)
         self.total_batches = max(n // bs, 1)
         self.n_steps = self.total_batches * local_epochs
-        if optimizer == "adam":
-            if model.cflat is model.flat:
-                raise RuntimeError("graphed Adam needs the bf16 shadow")
-            self.m = torch.zeros_like(model.flat)
-            self.v = torch.zeros_like(model.flat)
-            self.step_t = torch.zeros(1, device=model.device,
-                                      dtype=torch.int32)
-            self.bc = torch.zeros(2, device=model.device,
-                                  dtype=torch.float32)
-        elif optimizer == "sgdm":
-            self.sgdm = _sgdm_state(model, sgdm_cfg, lr_dev, p0)
-        elif optimizer != "sgd":
-            raise ValueError(optimizer)
-        self._lr = float(lr)
-        self._batches = [(shard_x[b * bs:(b + 1) * bs],
-                          shard_y[b * bs:(b + 1) * bs])
-                         for b in range(self.total_batches)] * local_epochs
+        self.opt = LocalOptimizer(model, optimizer, lr, True, sgdm_cfg,
+                                  lr_dev, p0)
+        batches = [(shard_x[b * bs:(b + 1) * bs],
+                    shard_y[b * bs:(b + 1) * bs])
+                   for b in range(self.total_batches)] * local_epochs
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        def warm():
             for _ in range(2):
-                self._one_step(*self._batches[0])
-        torch.cuda.current_stream().wait_stream(side)
-        self.model.zero_grad()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, pool=pool):
-            for xb, yb in self._batches:
-                self._one_step(xb, yb, accumulate=True)
+                train_step(model, self.opt, *batches[0])
 
-    def _optim_step(self) -> None:
-        if self.optimizer == "adam":
-            self.model.adam_step_graph(self.m, self.v, self.step_t,
-                                       self.bc, self._lr)
-        elif self.optimizer == "sgdm":
-            self.model.sgdm_step(self.sgdm)
-        else:
-            self.model.sgd_step(self._lr)
+        def whole_pass():
+            for xb, yb in batches:
+                train_step(model, self.opt, xb, yb, self.cost)
 
-    def _one_step(self, xb, yb, accumulate: bool = False) -> None:
-        self.model.zero_grad()
-        loss = self.model.loss(xb, yb)
-        loss.backward()
-        self._optim_step()
-        if accumulate:
-            self.cost.add_(loss.detach().float())
+        self.graph = _capture(warm, whole_pass, pool, zero_grad_of=model)
 
     def pool(self):
         return self.graph.pool()
@@ -232,12 +249,7 @@ class GraphedLocalTrain:
         round's global weights first (set_flat). Returns the summed
         per-batch loss (device scalar)."""
         self.cost.zero_()
-        if self.optimizer == "adam":
-            self.m.zero_()
-            self.v.zero_()
-            self.step_t.zero_()
-        elif self.optimizer == "sgdm":
-            self.sgdm.reset()
+        self.opt.reset()
         self.graph.replay()
         return self.cost
 
@@ -264,18 +276,15 @@ class GraphedScorePhase:
         # shadow directly (the eval forward's only weight consumer);
         # the fp32 master stays stale during scoring — every later
         # phase reloads it via set_flat (ops/functional.py score_load_)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            O.score_load_(model.cflat.data, global_flat, cand_stack[0], lr)
-            model.accuracy_t(shard_x, shard_y)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, pool=pool):
+        def score_slot(k: int) -> torch.Tensor:
+            O.score_load_(model.cflat.data, global_flat, cand_stack[k], lr)
+            return model.accuracy_t(shard_x, shard_y)
+
+        def all_slots():
             for k in range(self.K):
-                O.score_load_(model.cflat.data, global_flat,
-                              cand_stack[k], lr)
-                self.accs[k] = model.accuracy_t(shard_x, shard_y)
+                self.accs[k] = score_slot(k)
+
+        self.graph = _capture(lambda: score_slot(0), all_slots, pool)
 
     def pool(self):
         return self.graph.pool()
@@ -307,16 +316,15 @@ class GraphedScore:
         self.model = model
         self.cand = torch.empty_like(model.flat)
         self.cand.copy_(model.flat.detach())
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+
+        def load_and_score():
             model.set_flat(self.cand)
-            model.accuracy_t(shard_x, shard_y)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, pool=pool):
-            model.set_flat(self.cand)
-            self.acc = model.accuracy_t(shard_x, shard_y)
+            return model.accuracy_t(shard_x, shard_y)
+
+        def captured():
+            self.acc = load_and_score()
+
+        self.graph = _capture(load_and_score, captured, pool)
 
     def pool(self):
         return self.graph.pool()

@@ -204,3 +204,132 @@ def test_whole_phase_graphs_active_in_protocol_round():
     # the packed candidate stack exists and matches the quota
     assert eng._cand_stack is not None
     assert eng._cand_stack.shape[0] == cfg.needed_update_count
+
+
+# ------------------------------------------------ fallback routes
+def _fallback_cfg(**kw):
+    """Smallest protocol with several local participants per phase and
+    more than one batch per local pass."""
+    from bflc_amd.config import FLConfig
+    return FLConfig.for_world(8, model="mlp", n_features=32, n_class=8,
+                              samples_per_client=128, batch_size=64,
+                              eval_samples=128, **kw)
+
+
+def _selected(eng):
+    return tuple(o for o, _ in eng.last_decision.selected)
+
+
+def test_per_batch_stepper_when_whole_pass_capture_fails(monkeypatch):
+    """A failed whole-pass capture must leave the engine on the
+    per-batch GraphedTrainStep route (graphs stay on), with the same
+    committee selections and the same global model as the whole-pass
+    engine: both replay the same kernels in the same order."""
+    from bflc_amd.fl import graphs
+
+    def no_capture(*a, **kw):
+        raise RuntimeError("whole-pass capture unavailable (test)")
+
+    cfg = _fallback_cfg()
+    with monkeypatch.context() as mp:
+        mp.setattr(graphs, "GraphedLocalTrain", no_capture)
+        eng = _engine(cfg)
+        sel = []
+        with pytest.warns(UserWarning, match="whole-train graph capture"):
+            for _ in range(3):
+                eng.run_round()
+                sel.append(_selected(eng))
+    assert len(eng._steppers) > 0
+    assert eng._train_graphs and all(
+        g is None for g in eng._train_graphs.values())
+    assert eng._use_graphs
+
+    ref = _engine(cfg)
+    ref_sel = []
+    for _ in range(3):
+        ref.run_round()
+        ref_sel.append(_selected(ref))
+    assert any(g is not None for g in ref._train_graphs.values())
+    assert not ref._steppers
+    print(f"per-batch vs whole-pass: equal "
+          f"{torch.equal(eng.global_flat, ref.global_flat)} max |diff| "
+          f"{float((eng.global_flat - ref.global_flat).abs().max()):.3e}")
+    assert sel == ref_sel
+    assert torch.equal(eng.global_flat, ref.global_flat)
+
+
+def test_per_candidate_scoring_when_round_is_short_of_quota(monkeypatch):
+    """One forged update signature leaves a round one short of its
+    quota: the packed [quota, P] scoring graphs do not fit, so that
+    round scores on the per-candidate GraphedScore route, and the next
+    clean round is back on the packed graphs. Selections and the global
+    model match an eager engine fed the same forgery."""
+    from bflc_amd.chain.identity import KeyTable
+    from bflc_amd.fl import graphs
+
+    calls = {"candidate": 0, "packed": 0}
+    score_candidate = graphs.GraphedScore.score_candidate
+    run_inplace = graphs.GraphedScorePhase.run_inplace
+    run = graphs.GraphedScorePhase.run
+
+    def counted(fn, key):
+        def wrapper(self, *a, **kw):
+            calls[key] += 1
+            return fn(self, *a, **kw)
+        return wrapper
+
+    monkeypatch.setattr(graphs.GraphedScore, "score_candidate",
+                        counted(score_candidate, "candidate"))
+    monkeypatch.setattr(graphs.GraphedScorePhase, "run_inplace",
+                        counted(run_inplace, "packed"))
+    monkeypatch.setattr(graphs.GraphedScorePhase, "run",
+                        counted(run, "packed"))
+
+    def three_rounds(use_graphs):
+        cfg = _fallback_cfg(use_graphs=use_graphs)
+        eng = _engine(cfg)
+        orig = eng.keys
+        wrong = KeyTable(eng.origins, seed=999)  # attacker's keys
+
+        class SplitKeys:
+            """Sign ONE origin's update with the wrong key table;
+            verify with the true one."""
+            def __init__(self, victim):
+                self.victim = victim
+
+            def sign(self, kind, o, e, p):
+                forged = kind == "update" and o == self.victim
+                return (wrong if forged else orig).sign(kind, o, e, p)
+
+            def verify(self, *a):
+                return orig.verify(*a)
+
+        out = []
+        for r in range(3):
+            if r == 1:
+                eng.keys = SplitKeys(
+                    eng.origins[eng._planned_submitters()[0]])
+            before = dict(calls)
+            st = eng.run_round()
+            eng.keys = orig
+            out.append((st, _selected(eng),
+                        {k: calls[k] - before[k] for k in calls}))
+        return eng, cfg, out
+
+    eng, cfg, got = three_rounds(True)
+    quota = cfg.needed_update_count
+    assert [st.n_updates for st, _, _ in got] == [quota, quota - 1, quota]
+    assert 0 < got[1][0].n_updates < quota
+    # the short round ran on the per-candidate graphs, and only it did
+    assert any(g is not None for g in eng._scorers.values())
+    assert got[1][2]["candidate"] > 0 and got[1][2]["packed"] == 0
+    for r in (0, 2):  # clean rounds: the packed whole-phase graphs
+        assert got[r][2]["packed"] > 0 and got[r][2]["candidate"] == 0
+
+    ref, _, want = three_rounds(False)
+    assert not ref._scorers and not ref._score_graphs
+    print(f"per-candidate vs eager: equal "
+          f"{torch.equal(eng.global_flat, ref.global_flat)} max |diff| "
+          f"{float((eng.global_flat - ref.global_flat).abs().max()):.3e}")
+    assert [s for _, s, _ in got] == [s for _, s, _ in want]
+    assert torch.equal(eng.global_flat, ref.global_flat)

@@ -246,3 +246,59 @@ def test_engine_extended_differs_from_legacy_and_learns():
     ext.run(4)
     assert not torch.equal(legacy.global_flat, ext.global_flat)
     assert ext.evaluate_global() > 0.5  # 4 classes, chance 0.25
+
+
+# ------------------------------------------------------- optimizer object
+@pytest.mark.parametrize("kind,kw", [
+    ("adam", dict(optimizer="adam", learning_rate=0.001)),
+    ("sgdm", dict(momentum=0.9)),
+    ("sgd", {}),
+])
+def test_local_optimizer_reset_gives_a_fresh_pass(kind, kw):
+    """Fresh state per client pass: two steps, reset(), two steps from
+    the same restored weights must land on the same bits. A reset that
+    forgets Adam's (m, v, step) or the momentum buffer carries one
+    client's state into the next one's pass."""
+    from bflc_amd.data import make_federated
+    from bflc_amd.fl import graphs
+    from bflc_amd.models import build_model
+    cfg = FLConfig.for_world(1, **{**_BASE, **kw})
+    shard = make_federated(cfg)[0][0]
+    model = build_model(cfg, torch.device("cpu"))
+    model.init_params(cfg.seed)
+    start = model.get_flat()
+    lr_dev = torch.full((1,), cfg.learning_rate)
+    opt = graphs.LocalOptimizer(
+        model, kind, cfg.learning_rate, False,
+        **(dict(sgdm_cfg=cfg, lr_dev=lr_dev, p0=start)
+           if kind == "sgdm" else {}))
+    assert opt.kind == kind
+    bs = cfg.batch_size
+
+    def two_steps():
+        model.set_flat(start)
+        for b in range(2):
+            graphs.train_step(model, opt, shard.x[b * bs:(b + 1) * bs],
+                              shard.y[b * bs:(b + 1) * bs])
+        return model.get_flat()
+
+    first = two_steps()
+    assert not torch.equal(first, start)
+    if kind != "sgd":  # the state really carries over without a reset
+        assert not torch.equal(two_steps(), first)
+    opt.reset()
+    assert torch.equal(two_steps(), first)
+
+
+def test_local_optimizer_rejects_unknown_kind_and_fp32_graphed_adam():
+    from bflc_amd.fl import graphs
+    from bflc_amd.models import build_model
+    cfg = FLConfig.for_world(1, **_BASE)
+    model = build_model(cfg, torch.device("cpu"))
+    with pytest.raises(ValueError):
+        graphs.LocalOptimizer(model, "lion", 0.1, False)
+    with pytest.raises(ValueError):  # sgdm without its device lr
+        graphs.LocalOptimizer(model, "sgdm", 0.1, False)
+    assert model.cflat is model.flat  # fp32 on the CPU: no bf16 shadow
+    with pytest.raises(RuntimeError, match="bf16-shadow"):
+        graphs.LocalOptimizer(model, "adam", 0.1, True)
